@@ -8,10 +8,15 @@ residual adapters, 4 level taps + seg/det projections, fused anomaly map
 all-gathered over RCCL (the path's only exchange). Weights: random-init
 synthetic (no checkpoint in the image), bf16 compute.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with a
+Prints ONE JSON line on rank 0. A plain run sets up,
+warms up, times the K steps and prints the headline fields (`value`, `ms_per_step`, ...);
+--dump-outputs DIR also writes the last timed step's maps and scores as DIR/<name>.npy
+(same arguments -> same seeded inputs, so two builds compare output for output).
+Everything else runs only with --full: the timed outputs checked against the eager path
+and the CPU oracle (the parity gate and the exit status), the N-rank gather check, a
 `roofline` object for the dominant kernel (bf16 GEMM, MFMA-bound), a
 `roofline_map` object for the anomaly-map stream kernel (HBM-bound) and a
 `cpu_baseline` measured with the torch-CPU oracle (oracle/aaclip_torch.py: the
@@ -919,6 +924,32 @@ def modes_leg(vp, ad, x, T, steps: int, warmup: int, streams: int):
     return out
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: everything written stays under this
+
+
+def dump_outputs(path: str, maps, scores, scores_all=None) -> dict:
+    """--dump-outputs: what the timed path returned in its last timed step, as float32
+    .npy files under `path`: maps.npy [b, S, S] and scores.npy [b] (this rank's shard), and
+    for N > 1 scores_gathered.npy [n_total] (the all-gathered image scores). A map tensor
+    over the byte budget is written as a fixed sample instead: the flat elements at
+    numpy.random.default_rng(0).choice(maps.size, k, replace=False), sorted, as a 1-D array
+    (the same elements for the same shape in every run). Returns {name: shape} as written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    out = {"scores": scores.detach().float().cpu().numpy()}
+    if scores_all is not None:
+        out["scores_gathered"] = scores_all.detach().float().cpu().numpy()
+    m = maps.detach().float().cpu().numpy()
+    budget = DUMP_MAX_BYTES - sum(v.nbytes for v in out.values()) - 1024 * (len(out) + 1)  # .npy headers
+    if m.nbytes > budget:
+        keep = np.sort(np.random.default_rng(0).choice(m.size, budget // 4, replace=False))
+        m = m.reshape(-1)[keep]
+    out["maps"] = m
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
+    return {name: list(arr.shape) for name, arr in out.items()}
+
+
 def _streams_arg(v: str):
     """--streams N (equal chunks) or an explicit chunk-size list 'a,b,...' (summing to --batch)."""
     return tuple(int(t) for t in v.split(",")) if "," in v else int(v)
@@ -931,6 +962,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32, help="images per GPU per step")
     ap.add_argument("--img-size", type=int, default=336)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (output checks against the eager path and "
+                         "the CPU oracle + parity gate, N-rank gather check, rooflines, compute modes, CPU baseline "
+                         "and parity, preprocessing, metrics, C5); the --no-* / --cpu-seconds / --isolated switches "
+                         "below pick among those legs and mean nothing without --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0: maps, scores; N > 1 also the gathered scores) "
+                         "as float32 DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0,
                     help="steady-state seconds per CPU-baseline leg (0 = skip the CPU leg and parity)")
     ap.add_argument("--no-roofline", action="store_true")
@@ -949,6 +988,8 @@ def main():
     ap.add_argument("--dtype", choices=("bf16", "fp16"), default="bf16",
                     help="compute dtype of the timed step (C2 is quoted in bf16; fp16 = the contract mode, for A/B)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     n_streams = args.streams if isinstance(args.streams, int) else len(args.streams)  # for the other legs
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1026,17 +1067,19 @@ def main():
         dist.all_gather_into_tensor(t_all, torch.tensor([elapsed], device=dev, dtype=torch.float64))
         per_rank = [round(v / args.steps * 1e3, 3) for v in t_all.tolist()]
         elapsed = max(t_all.tolist())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, last[0], last[1], last[2] if world > 1 else None)
+    dist_check = None
+    if world > 1 and args.full:
         # the N-rank line proves its own result: own slices + a foreign shard recomputed
         # on rank 0 (eager, one stream: a different launch path from the timed graph)
         dist_check = verify_gather(lambda xi: eng.predict(xi, T, "Industrial", streams=1)[1].clone(), images_of,
                                    last[2], last[1], n_total)
         dist_check["ms_per_step_per_rank"] = per_rank
-    else:
-        dist_check = None
 
     images = n_total * args.steps
     ms_per_step = elapsed / args.steps * 1e3
-    ws = eng._workspace(B, S)
     line = {
         "metric": "images/sec (336x336, ViT-L/14) + pixel-AUROC parity vs CPU ref",
         "value": round(images / elapsed, 2),
@@ -1060,6 +1103,17 @@ def main():
                    "gflop_per_image": round(flops_per_image((S // 14) ** 2 + 1) / 1e9, 2)},
     }
     line["tflops_whole_path"] = round(flops_per_image((S // 14) ** 2 + 1) * images / elapsed / 1e12, 1)
+    if dumped is not None:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "float32": dumped}
+    if not args.full:
+        # the plain run ends here: set-up, warm-up, the timed steps, the dump, the line
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    ws = eng._workspace(B, S)
     if dist_check is not None:
         line["distributed"] = dist_check
     # the timed step's own outputs, checked after the fact: finite, and bit-identical to an

@@ -90,6 +90,26 @@ def test_gate_fails_without_any_parity_leg():
     assert rc == 1 and printed["parity_gate"] is False
 
 
+def test_dump_outputs_writes_float32_arrays_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: maps / scores (and the gathered scores) as float32 .npy, bit for bit;
+    a map over the byte budget becomes the same seeded sample of its elements in every call."""
+    g = torch.Generator().manual_seed(4)
+    maps, scores = torch.randn(3, 20, 20, generator=g), torch.rand(3, generator=g)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), maps, scores, torch.cat([scores, scores]))
+    assert shapes == {"scores": [3], "scores_gathered": [6], "maps": [3, 20, 20]}
+    got = np.load(tmp_path / "a" / "maps.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, maps.numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "scores.npy"), scores.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    for d in ("b", "c"):
+        shapes = bench.dump_outputs(str(tmp_path / d), maps, scores)
+        assert sorted(shapes) == ["maps", "scores"] and len(shapes["maps"]) == 1
+    b, c = np.load(tmp_path / "b" / "maps.npy"), np.load(tmp_path / "c" / "maps.npy")
+    assert np.array_equal(b, c) and 0 < b.size < maps.numel()
+    assert sum(f.stat().st_size for f in (tmp_path / "b").iterdir()) <= 4096
+    assert np.isin(b, maps.numpy()).all()
+
+
 def test_timed_step_vs_oracle_catches_a_corrupted_map():
     """The timed-step check end to end on the CPU: bench's own synthetic ViT-L/14 weights at a
     112 px image (8 x 8 patches), the CPU oracle's outputs standing in for the timed replay's; the

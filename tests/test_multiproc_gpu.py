@@ -28,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_two_ranks_real_engine(dev):
     env = dict(os.environ, AACLIP_BENCH_REHEARSAL="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-c5", "--no-modes", "--no-roofline", "--cpu-seconds", "0"]
+           "--full", "--no-c5", "--no-modes", "--no-roofline", "--cpu-seconds", "0"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -56,7 +56,7 @@ def test_bench_c3_partition_eight_ranks_real_engine(dev):
     number. Started as a fresh child process. Reference: test.py:53-99."""
     env = dict(os.environ, AACLIP_BENCH_REHEARSAL="1", MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "8", "--batch", "32", "--steps", "2",
-           "--warmup", "1", "--no-c5", "--no-modes", "--no-roofline", "--cpu-seconds", "0", "--streams", "1"]
+           "--warmup", "1", "--full", "--no-c5", "--no-modes", "--no-roofline", "--cpu-seconds", "0", "--streams", "1"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=840)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

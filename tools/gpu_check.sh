@@ -11,7 +11,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q --maxfail=20 --timeout 300
 rc=$?
 tail -5 $OUT/pytest.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "pytest rc=$rc: stopping"; exit $rc; fi
-timeout -k 10 900 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 900 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 rc2=$?
 tail -c 3000 $OUT/bench.json; tail -5 $OUT/bench.err
 exit $(( rc2 != 0 ? rc2 : rc ))

@@ -13,6 +13,6 @@ tail -3 $OUT/pytest.log
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "pytest rc=$rc: stopping"; exit $rc; fi
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo smoke failed; exit 3; }
 tail -1 $OUT/smoke.log
-timeout -k 10 900 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; tail -5 $OUT/bench.err; exit 4; }
+timeout -k 10 900 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { echo bench failed; tail -5 $OUT/bench.err; exit 4; }
 timeout -k 10 600 python -u tools/c4_synthetic.py --cpu-n 8 --out $OUT/c4.json > $OUT/c4.log 2>&1 || { echo c4 failed; exit 5; }
 exit $rc
