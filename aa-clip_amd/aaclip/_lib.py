@@ -10,7 +10,7 @@ import ctypes
 import os
 
 LIB_PATH = os.environ.get("AACLIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libaaclip_hip.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 F32 = 0
 BF16 = 1
@@ -24,6 +24,7 @@ EPI_AUX_BF16 = 16
 EPI_QGELU = 32
 ATTN_CAUSAL = 1
 ATTN_Q_PRESCALED = 2
+VV_MAX_BATCH = 64  # AACLIP_VV_MAX_BATCH
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -48,6 +49,7 @@ SIGNATURES = {
     "aaclip_gemm_concurrent": [_I, ctypes.POINTER(_I)],
     "aaclip_gemm_plan": [_I, _I, _I, _I],
     "aaclip_attention": [_I, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P],
+    "aaclip_vv_attention": [_I, _P, _L, _P, _L, _I, _I, _I, _I, _P],
     "aaclip_set_attn_variant": [_I],
     "aaclip_im2col": [_I, _P, _P, _I, _I, _I, _I, _I, _P],
     "aaclip_embed_ln": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _L, _P],

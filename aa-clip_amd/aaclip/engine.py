@@ -662,3 +662,181 @@ class TextEngine:
         for col, tok in enumerate((tok_normal, tok_abnormal)):
             ops.anchor_reduce(self.encode(tok), T, col)
         return T
+
+
+class FrozenVisualEngine:
+    """The frozen, forward-only CLIP image tower: CLIP.encode_image (reference
+    model/model.py:185-188 -> VisionTransformer.forward, model/transformer.py:490-551),
+    plain or after VisionTransformer.DAPM_replace (transformer.py:407-425).
+
+    Same packing, fp32 residual stream, embed_ln / block_tail row kernels and GEMM
+    epilogues as VisualEngine; no adapters. surgery_from = s (0..23) runs blocks s..23 as
+    the reference's post-surgery blocks: ln_1, a V-only projection (rows [2048:3072] of
+    in_proj: the q / k thirds are computed and discarded by the reference, never here),
+    ops.vv_attention, out-proj + residual, ln_2 + MLP. That attention mixes the IMAGES of
+    a batch (per token position and head; see aaclip_vv_attention), so a surgery batch is
+    never cut into chunks or spread over streams, and holds at most ops.VV_MAX_BATCH
+    images. Without surgery every image is independent and batches above max_chunk run
+    as consecutive chunks."""
+
+    def __init__(self, vparams: dict, *, dtype=torch.float16, surgery_from: int | None = None, quick_gelu=False):
+        if dtype not in (torch.bfloat16, torch.float16, torch.float32):
+            raise ValueError("FrozenVisualEngine dtype must be bfloat16, float16 or float32 (no fp8 mode)")
+        if surgery_from is not None and not 0 <= int(surgery_from) < LAYERS:
+            raise ValueError(f"surgery_from must be a block index in 0..{LAYERS - 1} or None")
+        self.act = "quick" if quick_gelu else True
+        self.dtype = dtype
+        self.surgery_from = LAYERS if surgery_from is None else int(surgery_from)
+        dev = vparams["visual.conv1.weight"].device
+        if dev.type != "cuda":
+            raise RuntimeError("FrozenVisualEngine needs device tensors (no CPU path)")
+        self.device = dev
+        f32 = lambda t: t.detach().to(dev, torch.float32).contiguous()  # noqa: E731
+        cdt = lambda t: t.detach().to(dev, dtype).contiguous()  # noqa: E731
+        w = vparams["visual.conv1.weight"].detach().reshape(WIDTH, -1)
+        conv = torch.zeros(WIDTH, KPATCH, device=dev, dtype=torch.float32)
+        conv[:, : w.shape[1]] = w
+        self.conv = conv.to(dtype).contiguous()
+        self.cls = f32(vparams["visual.class_embedding"])
+        self.pos = f32(vparams["visual.positional_embedding"])
+        self.ln_pre = (f32(vparams["visual.ln_pre.weight"]), f32(vparams["visual.ln_pre.bias"]))
+        self.ln_post = (f32(vparams["visual.ln_post.weight"]), f32(vparams["visual.ln_post.bias"]))
+        self.w_proj = cdt(vparams["visual.proj"].detach().t())  # x @ proj == x . (proj^T)^T
+        self.q_prescaled = dtype != torch.float32  # log2(e)/8 folded into the Q rows (as VisualEngine)
+        self.blocks = []
+        for i in range(LAYERS):
+            p = f"visual.transformer.resblocks.{i}."
+            w_in = vparams[p + "attn.in_proj_weight"].detach().to(dev, torch.float32)
+            b_in = vparams[p + "attn.in_proj_bias"].detach().to(dev, torch.float32)
+            if i >= self.surgery_from:  # V rows only; the Q fold touches rows [:1024], so V is as loaded
+                w_in, b_in = w_in[2 * WIDTH:], b_in[2 * WIDTH:]
+            elif self.q_prescaled:
+                w_in, b_in = w_in.clone(), b_in.clone()
+                w_in[:WIDTH] *= Q_LOG2_SCALE
+                b_in[:WIDTH] *= Q_LOG2_SCALE
+            self.blocks.append(dict(
+                ln1=(f32(vparams[p + "ln_1.weight"]), f32(vparams[p + "ln_1.bias"])),
+                ln2=(f32(vparams[p + "ln_2.weight"]), f32(vparams[p + "ln_2.bias"])),
+                w_in=cdt(w_in), b_in=b_in.contiguous(),
+                w_o=cdt(vparams[p + "attn.out_proj.weight"]), b_o=f32(vparams[p + "attn.out_proj.bias"]),
+                w_fc=cdt(vparams[p + "mlp.c_fc.weight"]), b_fc=f32(vparams[p + "mlp.c_fc.bias"]),
+                w_pr=cdt(vparams[p + "mlp.c_proj.weight"]), b_pr=f32(vparams[p + "mlp.c_proj.bias"]),
+            ))
+        self._ws = {}
+        self._patch = None
+        self.poison = False  # tests: fill new workspaces with NaN (read-before-write screen)
+
+    @property
+    def surgery(self) -> bool:
+        return self.surgery_from < LAYERS
+
+    max_chunk = staticmethod(VisualEngine.max_chunk)
+
+    def _workspace(self, B: int, S: int):
+        key = (B, S)
+        if key in self._ws:
+            return self._ws[key]
+        g = S // PATCH
+        P = g * g
+        n_tok = P + 1
+        if self.pos.shape[0] != n_tok:
+            raise ValueError(f"positional embedding has {self.pos.shape[0]} rows, image needs {n_tok} "
+                             "(resize it at load time, reference model/model.py:395-426)")
+        R = B * n_tok
+        dev, cdt = self.device, self.dtype
+        e = lambda *s, dt=cdt: torch.empty(*s, device=dev, dtype=dt)  # noqa: E731
+        ws = dict(
+            P=P, n_tok=n_tok, cols=e(B * P, KPATCH), x=e(R, WIDTH, dt=torch.float32), h=e(R, WIDTH),
+            qkv=e(R, 3 * WIDTH) if self.surgery_from > 0 else None,  # the standard blocks' packed [q|k|v]
+            v=e(R, WIDTH) if self.surgery else None,                 # the surgery blocks' V projection
+            attn=e(R, WIDTH), fc=e(R, 4 * WIDTH),
+            tap=e(B * P, WIDTH),  # ln_post of the patch rows after block 24 (patch_features)
+            cls_h=e(B, WIDTH),    # ln_post of the CLS rows
+        )
+        if self._ws and not torch.cuda.is_current_stream_capturing():
+            torch.cuda.synchronize(self.device)
+        self._ws.clear()  # one resident shape: the frozen paths run one batch shape per stage
+        self._ws[key] = ws
+        if self.poison:
+            for t in ws.values():
+                if isinstance(t, torch.Tensor):
+                    t.fill_(float("nan"))
+        return ws
+
+    def _encode_chunk(self, x: torch.Tensor, out_layers, want_patch: bool):
+        B, _, S, _ = x.shape
+        ws = self._workspace(B, S)
+        P, n_tok = ws["P"], ws["n_tok"]
+        X, H = ws["x"], ws["h"]
+        ops.im2col(x, ws["cols"], PATCH)
+        ops.gemm(ws["cols"], self.conv, X, row_group=P, row_group_out=n_tok, row_offset=1)
+        ops.embed_ln(X, self.cls, self.pos, self.ln_pre, self.blocks[0]["ln1"], H, B, n_tok)
+        tokens = []
+        for i, blk in enumerate(self.blocks):
+            if i >= self.surgery_from:
+                ops.gemm(H, blk["w_in"], ws["v"], bias=blk["b_in"])
+                ops.vv_attention(ws["v"], ws["attn"], B, n_tok, HEADS)
+            else:
+                ops.gemm(H, blk["w_in"], ws["qkv"], bias=blk["b_in"])
+                ops.attention(ws["qkv"], ws["attn"], B, n_tok, HEADS, q_prescaled=self.q_prescaled)
+            ops.gemm(ws["attn"], blk["w_o"], X, bias=blk["b_o"], residual=X)
+            ops.layernorm(X, blk["ln2"][0], blk["ln2"][1], H)
+            ops.gemm(H, blk["w_fc"], ws["fc"], bias=blk["b_fc"], gelu=self.act)
+            ops.gemm(ws["fc"], blk["w_pr"], X, bias=blk["b_pr"], residual=X)
+            if i + 1 in out_layers:
+                tokens.append(X.view(B, n_tok, WIDTH).clone())
+            if i + 1 < LAYERS:
+                ops.block_tail(X, n_tok, ln=self.blocks[i + 1]["ln1"], h=H)
+            elif want_patch:
+                ops.block_tail(X, n_tok, post=self.ln_post, tap=ws["tap"])
+        # pooled = ln_post(x[:, 0]) @ proj: the CLS rows are read in place (row stride n_tok * width)
+        ops.layernorm(X.view(B, n_tok * WIDTH)[:, :WIDTH], self.ln_post[0], self.ln_post[1], ws["cls_h"])
+        pooled = torch.empty(B, EMBED, device=self.device, dtype=torch.float32)
+        ops.gemm(ws["cls_h"], self.w_proj, pooled)
+        patch = None
+        if want_patch:
+            patch = torch.empty(B * P, EMBED, device=self.device, dtype=torch.float32)
+            ops.gemm(ws["tap"], self.w_proj, patch)
+            patch = patch.view(B, P, EMBED)
+        return pooled, tokens, patch
+
+    @staticmethod
+    def chunk_bounds(B: int, max_chunk: int) -> list:
+        """[b0, b1) image ranges a plain (per-image) batch of B runs as."""
+        return [(b0, min(B, b0 + max_chunk)) for b0 in range(0, B, max_chunk)]
+
+    @torch.no_grad()
+    @_on_device
+    def encode(self, x: torch.Tensor, out_layers=(), patch_features: bool = False):
+        """VisionTransformer.forward: (pooled [B, 768] fp32, [x after block i as a fresh
+        [B, n_tok, 1024] fp32 tensor for each i in 1..24 that is in out_layers, ascending]).
+        All 24 blocks always run. patch_features=True also keeps ln_post(patch rows after
+        block 24) @ proj for patch_features() (AdaptedCLIP.forward_original)."""
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[2] % PATCH:
+            raise ValueError("input must be [B, 3, S, S] with S a multiple of 14")
+        out_layers = set(int(i) for i in out_layers)
+        x = x.to(self.device, torch.float32).contiguous()
+        B, S = x.shape[0], x.shape[-1]
+        if self.surgery:
+            if B > ops.VV_MAX_BATCH:
+                raise ValueError(f"a surgery tower couples the images of a batch and takes at most "
+                                 f"{ops.VV_MAX_BATCH} images at once, got {B}")
+            bounds = [(0, B)]
+        else:
+            bounds = self.chunk_bounds(B, self.max_chunk(S))
+        parts = [self._encode_chunk(x[b0:b1], out_layers, patch_features) for b0, b1 in bounds]
+        if len(parts) == 1:
+            pooled, tokens, patch = parts[0]
+        else:
+            pooled = torch.cat([p[0] for p in parts])
+            tokens = [torch.cat(level) for level in zip(*(p[1] for p in parts))]
+            patch = torch.cat([p[2] for p in parts]) if patch_features else None
+        self._patch = patch
+        return pooled, tokens
+
+    def patch_features(self) -> torch.Tensor:
+        """[B, P, 768] fp32: ln_post(patch tokens after block 24) @ proj of the last
+        encode(..., patch_features=True) (reference model/adapter.py:57-62)."""
+        if self._patch is None:
+            raise RuntimeError("patch_features() follows encode(x, out_layers, patch_features=True)")
+        return self._patch

@@ -393,6 +393,41 @@ def attention(qkv: torch.Tensor, out: torch.Tensor, batch: int, seq: int, heads:
     return out
 
 
+VV_MAX_BATCH = _lib.VV_MAX_BATCH
+
+
+def vv_attention(v: torch.Tensor, out: torch.Tensor, batch: int, n_tok: int, heads: int) -> torch.Tensor:
+    """out = v-v "surgery" attention ACROSS THE IMAGES of the batch, per token position and
+    head (aaclip_vv_attention; reference model/transformer.py:125-152 on the tower's
+    [L, N, D] layout). v: [batch*n_tok, heads*64] rows with unit column stride: its own
+    buffer or a column view (the V third) of a packed qkv buffer; out likewise, same
+    dtype, not overlapping v."""
+    _dev(v, out)
+    _rowmajor(v, "v")
+    _rowmajor(out, "out")
+    hd = 64
+    if v.shape != (batch * n_tok, heads * hd) or out.shape != v.shape:
+        raise ValueError("vv_attention shape mismatch")
+    if v.dtype != out.dtype:
+        raise ValueError("vv_attention tensors must share a dtype")
+    if not 1 <= batch <= VV_MAX_BATCH:
+        raise ValueError(f"vv_attention couples the images of a batch: 1..{VV_MAX_BATCH} images, got {batch}")
+    vec = 16 // v.element_size()
+    for t, n in ((v, "v"), (out, "out")):
+        if t.stride(0) < heads * hd or t.stride(0) % vec or t.data_ptr() % 16:
+            raise ValueError(f"vv_attention: {n} needs a row stride >= {heads * hd} that is a multiple of {vec} "
+                             "elements, and a 16-byte aligned start")
+    lo, hi = v.data_ptr(), v.data_ptr() + ((v.shape[0] - 1) * v.stride(0) + v.shape[1]) * v.element_size()
+    olo, ohi = out.data_ptr(), out.data_ptr() + ((out.shape[0] - 1) * out.stride(0) + out.shape[1]) * out.element_size()
+    if lo < ohi and olo < hi:
+        raise ValueError("vv_attention: out must not overlap v")
+    nbytes = 2 * v.shape[0] * v.shape[1] * v.element_size()
+    _launch("vv_attention", "vv_attention_kernel", 4.0 * batch * batch * hd * n_tok * heads, nbytes,
+            "aaclip_vv_attention", dtag(v), _ptr(v), v.stride(0), _ptr(out), out.stride(0), batch, n_tok, heads, hd,
+            _stream())
+    return out
+
+
 # ------------------------------------------------------------------------ rows
 def im2col(img: torch.Tensor, cols: torch.Tensor, patch: int) -> torch.Tensor:
     _dev(img, cols)

@@ -93,9 +93,15 @@ class AdaptedCLIP(nn.Module):
 
     # ------------------------------------------------------------------ API
     def forward_original(self, x, modality="visual"):
+        """([patch features [B, P, 768]], cls [B, 768]) of the un-adapted CLIP tower, fp32."""
         if modality != "visual":
             raise ValueError("modality must be visual")
-        raise NotImplementedError("forward_original (plain CLIP patch tokens) is not on the AA-CLIP eval path")
+        # reference model/adapter.py:55-63: encode_image(x, [24]), then ln_post and proj of the
+        # patch tokens; the frozen engine (following a DAPM_replace made on clipmodel.visual)
+        # taps and projects them itself, in self.compute_dtype
+        eng = self.clipmodel.visual.frozen_engine(self.compute_dtype)
+        cls_features, _ = eng.encode(x, [], patch_features=True)
+        return [eng.patch_features()], cls_features
 
     def forward(self, x):
         """(list[len(levels)] of [B, P, 768] unit-norm patch features, det [B, 768])."""

@@ -99,6 +99,57 @@ class VisionTransformer(nn.Module):
         self.embed_dim, self.num_heads = width, heads
         self.ln_post = nn.LayerNorm(width)
         self.proj = nn.Parameter(scale * torch.randn(width, output_dim))
+        self.DPAM_layer = None  # DAPM_replace bookkeeping
+        self._frozen = {}       # compute dtype -> (signature, FrozenVisualEngine)
+
+    @torch.no_grad()
+    def DAPM_replace(self, DPAM_layer):
+        """Reference transformer.py:407-425: `for i in range(1, DPAM_layer)` rewrites
+        resblocks[-i], i.e. the LAST DPAM_layer - 1 blocks, to the v-v attention of
+        transformer.py:125-152. Here the layer is recorded and the frozen engine runs those
+        blocks through ops.vv_attention; the parameters keep their in_proj_* / out_proj.*
+        names (the reference's post-surgery state dict renames them attn.qkv.* /
+        attn.proj.*). None or 1: no surgery. Above layers + 1 the reference runs off the
+        block list with an IndexError; here a ValueError."""
+        if DPAM_layer is None:
+            return
+        k, layers = int(DPAM_layer), self.transformer.layers
+        if k > layers + 1:
+            raise ValueError(f"DPAM_layer {k} rewrites {k - 1} blocks, the tower has {layers}")
+        if k >= 2 and (self.DPAM_layer is None or k > self.DPAM_layer):
+            self.DPAM_layer = k
+
+    @property
+    def surgery_blocks(self) -> range:
+        """Block indices DAPM_replace rewrote (empty without surgery)."""
+        layers = self.transformer.layers
+        return range(layers, layers) if self.DPAM_layer is None else range(layers - (self.DPAM_layer - 1), layers)
+
+    def frozen_engine(self, dtype=None):
+        """The HIP engine of the frozen tower, cached on the parameter signature, the DPAM
+        layer and the compute dtype (AACLIP_DTYPE, default fp16, unless given)."""
+        from aaclip.engine import FrozenVisualEngine
+        from .adapter import _default_dtype, param_signature
+        dtype = dtype or _default_dtype()
+        sig = (param_signature(self), self.DPAM_layer)
+        hit = self._frozen.get(dtype)
+        if hit is None or hit[0] != sig:
+            blocks = self.surgery_blocks
+            vp = {"visual." + k: v for k, v in self.state_dict().items()}
+            hit = (sig, FrozenVisualEngine(vp, dtype=dtype, surgery_from=blocks[0] if len(blocks) else None,
+                                           quick_gelu=self.transformer.quick_gelu))
+            self._frozen = {d: e for d, e in self._frozen.items() if e[0] == sig}  # drop stale packings
+            self._frozen[dtype] = hit
+        return hit[1]
+
+    def _global_pool(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Reference transformer.py:484-488 (no average pooling in this config): CLS, patches."""
+        return x[:, 0], x[:, 1:]
+
+    def forward(self, x: torch.Tensor, out_layers: list):
+        """Reference transformer.py:490-551 on the frozen HIP engine: (pooled [B, 768],
+        [tokens [B, n_tok, 1024] after block i for i in out_layers]), fp32 device tensors."""
+        return self.frozen_engine().encode(x, out_layers)
 
 
 class CLIP(nn.Module):
@@ -165,8 +216,13 @@ class CLIP(nn.Module):
         return x
 
     def encode_image(self, image, out_layers, normalize: bool = False):
-        raise NotImplementedError("CLIP.encode_image (forward_original) is not on the AA-CLIP eval path; "
-                                  "use AdaptedCLIP.forward")
+        """CLIP.encode_image (reference model/model.py:185-188): (pooled, patch_tokens) of
+        the frozen image tower, after DAPM_replace the surgery tower. normalize=True fails
+        in the reference too (F.normalize on that tuple)."""
+        if normalize:
+            raise ValueError("encode_image returns a (pooled, patch_tokens) tuple; normalize=True is not defined "
+                             "on it (the reference's F.normalize fails there too)")
+        return self.visual(image, out_layers)
 
 
 def resize_pos_embed(state_dict, model, interpolation: str = "bicubic", antialias: bool = True):

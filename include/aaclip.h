@@ -51,7 +51,7 @@ extern "C" {
 
 /* ABI version (bumped on any signature change; 2 = MX fp8 LayerNorm outputs, 3 = fp16 dtype,
  * aaclip_patch_logits, any-size blur_upsample; 6 = round 5: the rejected A/B entry points
- * removed, aaclip_trace_buffer added) and the target. */
+ * removed, aaclip_trace_buffer added; 8 = aaclip_vv_attention) and the target. */
 int aaclip_abi_version(void);
 const char* aaclip_arch(void);
 
@@ -246,6 +246,28 @@ int aaclip_attention(int dtype, const void* qkv, void* out, int batch, int seq,
 /* dtype AACLIP_FP8: bf16 qkv in, out written as MX e4m3 [batch*seq, heads*64] with one
  * e8m0 scale per (row, head) in out_mx [heads/2][ld_mx >= batch*seq][2] (the out-proj
  * A operand of aaclip_gemm_fp8mx, config C5); out_mx ignored otherwise. */
+
+/*
+ * v-v "surgery" attention of the frozen tower: the attention the reference's
+ * Attention module (model/transformer.py:125-152) computes once
+ * VisionTransformer.DAPM_replace (transformer.py:407-425) has put it into a block,
+ * x = softmax(v v^T / sqrt(d)) v (the q.k path is computed and discarded there, never
+ * here). That module receives the tower's [L, N, D] layout and unpacks it as [B, N, C],
+ * so the softmax runs across the IMAGES of the batch, separately for every token
+ * position t and head h: out[b,t,h] = sum_c softmax_c(v[b,t,h].v[c,t,h] / 8) v[c,t,h].
+ * v: first V column of row 0; row b*n_tok + t holds heads*head_dim columns, row stride
+ * ld_v elements (a [R, heads*64] buffer, or the V third of a packed [R, 3*heads*64]
+ * qkv buffer). out: [R, heads*64], row stride ld_out; must not alias v. dtype F32,
+ * BF16 or F16 (input and output alike); arithmetic is fp32, the 1/sqrt(64) scale is
+ * applied inside. head_dim must be 64, batch 1..AACLIP_VV_MAX_BATCH (one lane per image),
+ * ld_* >= heads*64 and a multiple of the 128-bit vector (8 elements in the 16-bit types,
+ * 4 in fp32), pointers 16-byte aligned, batch*n_tok and n_tok*ceil(heads/4) (the grid)
+ * < 2^31 and either operand's byte extent < 2^46. Fixed reduction order, no atomics: a token's result does not depend
+ * on the other tokens of the launch, and two launches give the same bits.
+ */
+#define AACLIP_VV_MAX_BATCH 64
+int aaclip_vv_attention(int dtype, const void* v, int64_t ld_v, void* out, int64_t ld_out,
+                        int batch, int n_tok, int heads, int head_dim, void* stream);
 
 /* Tuning hook for the 16-bit attention kernel: 0 = default (3), 1 = 4 waves x 32 queries per
  * workgroup, 2 = 2 waves x 64 queries, 3 = 1 with each full key tile phase-split so one
