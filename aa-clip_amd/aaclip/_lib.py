@@ -64,6 +64,12 @@ SIGNATURES = {
     "aaclip_patch_scores": [_I, _P, _I, _L, _P, _I, _I, _I, _I, _I, _P, _P],
     "aaclip_patch_logits": [_I, _P, _L, _P, _I, _I, _I, _I, _P, _P],
     "aaclip_blur_upsample": [_P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
+    "aaclip_patch_logits_per_image": [_I, _P, _L, _P, _L, _I, _I, _I, _I, _P, _P],
+    "aaclip_seg_loss": [_P, _P, _I, _I, _P, ctypes.c_size_t, _P, _P, _P],
+    "aaclip_seg_loss_bwd": [_P, _P, _P, _P, _I, _I, _P, _P],
+    "aaclip_upsample_softmax_bwd": [_P, _P, _I, _I, _I, _I, _P, _P],
+    "aaclip_patch_logits_bwd_workspace": [_I, _I, ctypes.POINTER(ctypes.c_size_t)],
+    "aaclip_patch_logits_bwd": [_I, _P, _L, _P, _L, _I, _P, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P],
     "aaclip_anomaly_map": [_I, _P, _I, _L, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P],
     "aaclip_image_score": [_I, _P, _L, _P, _I, _I, _I, _I, _P, _P, _P, _P],
     "aaclip_metrics_workspace": [_L, _I, ctypes.POINTER(ctypes.c_size_t)],

@@ -587,6 +587,150 @@ def blur_upsample(grid, out, *, ksize, sigma, softmax=False):
     return out
 
 
+# ------------------------------------------------------------------------ stage-1 loss head
+SEGLOSS_CHUNK = 4096   # AACLIP_SEGLOSS_CHUNK
+LOGITS_BWD_ROWS = 16   # AACLIP_LOGITS_BWD_ROWS
+
+
+def _f32c(t, name, shape=None):
+    if t.dtype != torch.float32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{name} must be contiguous fp32" + (f" {list(shape)}" if shape is not None else ""))
+
+
+def _anchors(T, C, batch, n_anchor=None):
+    """(t_stride, n_anchor) of shared [C, n] or per-image [batch, C, n] contiguous fp32 anchors."""
+    if T.dim() not in (2, 3) or T.dtype != torch.float32 or not T.is_contiguous() or T.shape[-2] != C:
+        raise ValueError("T must be contiguous fp32 [C, n_anchor] or [batch, C, n_anchor]")
+    if T.dim() == 3 and T.shape[0] != batch:
+        raise ValueError(f"per-image anchors need one set per image: got {T.shape[0]} for a batch of {batch}")
+    n = T.shape[-1]
+    if n_anchor is not None and n != n_anchor:
+        raise ValueError(f"this op takes {n_anchor} anchors, got {n}")
+    return (C * n if T.dim() == 3 else 0), n
+
+
+def patch_logits_per_image(f, T, out, *, group):
+    """Train-branch logits with shared [C, n] or per-image [B, C, n] anchors (n <= 8):
+    out [B, n, group] = 100 * f[b] . T[b]. A shared T gives patch_logits' bits."""
+    _dev(f, T, out)
+    _rowmajor(f, "f")
+    rows, C = f.shape
+    if group <= 0 or rows % group:
+        raise ValueError("group = patches per image must divide the rows")
+    t_stride, n = _anchors(T, C, rows // group)
+    if not 1 <= n <= 8:
+        raise ValueError(f"patch_logits_per_image supports 1..8 anchors, got {n}")
+    if out.numel() < rows * n or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("patch_logits_per_image output too small / not contiguous fp32")
+    nb = rows * C * f.element_size() + T.numel() * 4 + rows * n * 4
+    _launch("segloss", "patch_logits_per_image", 2.0 * rows * C * n, nb, "aaclip_patch_logits_per_image", dtag(f),
+            _ptr(f), f.stride(0), _ptr(T), t_stride, n, rows, C, group, _ptr(out), _stream())
+    return out
+
+
+def seg_loss_workspace(B: int, S: int, device) -> torch.Tensor:
+    return torch.empty(B * (-(-S * S // SEGLOSS_CHUNK)) * 8, device=device, dtype=torch.float64)
+
+
+def seg_loss(probs, mask, *, sums=None, loss=None, workspace=None):
+    """FocalLoss() + the two BinaryDiceLoss() of forward_utils.py:219-227. probs [B, 2, S, S],
+    mask [B, S, S] fp32 in [0, 1] -> (sums [B, 8] fp64, loss [4] fp32 = focal, dice0, dice1, total)."""
+    _dev(probs, mask, sums, loss, workspace)
+    if probs.dim() != 4 or probs.shape[1] != 2 or probs.shape[2] != probs.shape[3]:
+        raise ValueError("probs must be [B, 2, S, S]")
+    B, _, S, _ = probs.shape
+    _f32c(probs, "probs")
+    _f32c(mask, "mask", (B, S, S))
+    if sums is None:
+        sums = torch.empty(B, 8, device=probs.device, dtype=torch.float64)
+    if loss is None:
+        loss = torch.empty(4, device=probs.device, dtype=torch.float32)
+    if workspace is None:
+        workspace = seg_loss_workspace(B, S, probs.device)
+    if sums.dtype != torch.float64 or tuple(sums.shape) != (B, 8) or not sums.is_contiguous():
+        raise ValueError("sums must be contiguous fp64 [B, 8]")
+    if workspace.dtype != torch.float64 or not workspace.is_contiguous():
+        raise ValueError("seg_loss workspace must be contiguous fp64")
+    _f32c(loss, "loss", (4,))
+    _launch("segloss", "seg_loss", 0.0, 3.0 * B * S * S * 4, "aaclip_seg_loss", _ptr(probs), _ptr(mask), B, S,
+            _ptr(workspace), workspace.numel() * 8, _ptr(sums), _ptr(loss), _stream())
+    return sums, loss
+
+
+def seg_loss_bwd(probs, mask, sums, dloss, dprobs=None):
+    """dprobs [B, 2, S, S] = dloss * d total / d probs; dloss is a device fp32 scalar."""
+    _dev(probs, mask, sums, dloss, dprobs)
+    if probs.dim() != 4 or probs.shape[1] != 2 or probs.shape[2] != probs.shape[3]:
+        raise ValueError("probs must be [B, 2, S, S]")
+    B, _, S, _ = probs.shape
+    _f32c(probs, "probs")
+    _f32c(mask, "mask", (B, S, S))
+    if sums.dtype != torch.float64 or tuple(sums.shape) != (B, 8) or not sums.is_contiguous():
+        raise ValueError("sums must be contiguous fp64 [B, 8]")
+    if dloss.dtype != torch.float32 or dloss.numel() != 1:
+        raise ValueError("dloss must be one fp32 device scalar")
+    if dprobs is None:
+        dprobs = torch.empty_like(probs)
+    _f32c(dprobs, "dprobs", probs.shape)
+    _launch("segloss", "seg_loss_bwd", 0.0, 5.0 * B * S * S * 4, "aaclip_seg_loss_bwd", _ptr(probs), _ptr(mask),
+            _ptr(sums), _ptr(dloss), B, S, _ptr(dprobs), _stream())
+    return dprobs
+
+
+def upsample_softmax_bwd(grid, dprobs, dgrid=None):
+    """Backward of blur_upsample(ksize=0, softmax=True) for two channels: grid [B, 2, g, g]
+    (the logits the forward took), dprobs [B, 2, S, S] -> dgrid [B, 2, g, g]."""
+    _dev(grid, dprobs, dgrid)
+    if grid.dim() != 4 or grid.shape[2] != grid.shape[3] or dprobs.dim() != 4 or dprobs.shape[2] != dprobs.shape[3]:
+        raise ValueError("upsample_softmax_bwd takes grid [B, 2, g, g] and dprobs [B, 2, S, S]")
+    B, C, g, _ = grid.shape
+    S = dprobs.shape[-1]
+    if C != 2:
+        raise ValueError(f"upsample_softmax_bwd supports 2 channels, got {C}")
+    _f32c(grid, "grid")
+    _f32c(dprobs, "dprobs", (B, C, S, S))
+    if dgrid is None:
+        dgrid = torch.empty_like(grid)
+    _f32c(dgrid, "dgrid", grid.shape)
+    _launch("segloss", "upsample_softmax_bwd", 0.0, (2.0 * B * S * S + 4.0 * B * g * g) * 4,
+            "aaclip_upsample_softmax_bwd", _ptr(grid), _ptr(dprobs), B, C, g, S, _ptr(dgrid), _stream())
+    return dgrid
+
+
+def patch_logits_bwd_workspace(rows: int, group: int, device) -> torch.Tensor:
+    nbytes = ctypes.c_size_t(0)
+    call("aaclip_patch_logits_bwd_workspace", rows, group, ctypes.byref(nbytes))
+    return torch.empty(int(nbytes.value) // 4, device=device, dtype=torch.float32)
+
+
+def patch_logits_bwd(f, T, dgrid, *, group, need_dT=True, need_df=True, workspace=None):
+    """Backward of the two-anchor train logits: returns (dT, df), None for the one not asked for.
+    dT has T's shape ([C, 2] shared: summed over the images; [B, C, 2] per image), df is fp32 [rows, C]."""
+    _dev(f, T, dgrid, workspace)
+    _rowmajor(f, "f")
+    rows, C = f.shape
+    if group <= 0 or rows % group:
+        raise ValueError("group = patches per image must divide the rows")
+    if not (need_dT or need_df):
+        raise ValueError("patch_logits_bwd: ask for dT, df or both")
+    B = rows // group
+    t_stride, _ = _anchors(T, C, B, n_anchor=2)
+    if dgrid.numel() != rows * 2:
+        raise ValueError("dgrid must be [B, 2, group]")
+    _f32c(dgrid, "dgrid")
+    dT = torch.empty_like(T) if need_dT else None
+    df = torch.empty(rows, C, device=f.device, dtype=torch.float32) if need_df else None
+    if need_dT and workspace is None:
+        workspace = patch_logits_bwd_workspace(rows, group, f.device)
+    if workspace is not None and (workspace.dtype != torch.float32 or not workspace.is_contiguous()):
+        raise ValueError("patch_logits_bwd workspace must be contiguous fp32")
+    nb = (rows * C * f.element_size() if need_dT else 0) + (rows * C * 4 if need_df else 0) + rows * 2 * 4
+    _launch("segloss", "patch_logits_bwd", 4.0 * rows * C * (int(need_dT) + int(need_df)), nb,
+            "aaclip_patch_logits_bwd", dtag(f), _ptr(f), f.stride(0), _ptr(T), t_stride, 2, _ptr(dgrid), rows, C,
+            group, _ptr(workspace), 0 if workspace is None else workspace.numel() * 4, _ptr(dT), _ptr(df), _stream())
+    return dT, df
+
+
 def anomaly_map(levels, T, out, grid_ws, *, g, ksize, sigma, normalize=True):
     """Test-branch map of all levels: patch_scores into grid_ws (>= B*g*g fp32), then blur_upsample."""
     _dev(*levels, T, out, grid_ws)

@@ -118,12 +118,16 @@ __global__ __launch_bounds__(256) void patch_scores_kernel(LevelPtrs lv, int nl,
 // Train-branch logits for any number of anchors (forward_utils.py:199-202 with
 // C anchors): out[b, a, p] = 100 * f[b*group + p] . T[:, a], channel-major so it
 // feeds blur_upsample directly. One wave per patch row, anchors in sequence.
+// t_stride: the anchors of image b = row / group start at T + b * t_stride (0 = one
+// shared set); aaclip_patch_logits and aaclip_patch_logits_per_image launch this one
+// kernel, so a shared set gives the same bits through either.
 __global__ __launch_bounds__(256) void patch_logits_kernel(int in_dtype, const void* f, int64_t ld,
-                                                           const float* T, int n_anchor, int rows,
-                                                           int group, float* out) {
+                                                           const float* T, int64_t t_stride, int n_anchor,
+                                                           int rows, int group, float* out) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
+  T += (size_t)(row / group) * t_stride;
   float4_t v[3];
   if (in_dtype == AACLIP_F32) {
     const float* p = (const float*)f + (size_t)row * ld;
@@ -250,11 +254,8 @@ __device__ __forceinline__ void blur_band(const float* grid, float* out, int b, 
     for (int p = 0; p < 8; ++p) {
       const int x = cx + (vec4 ? 4 * lane + 256 * (p >> 2) + (p & 3) : lane + 64 * p);
       ok[p] = x < S;
-      const float sx = scale * (float)x;
-      const int ix0 = (int)sx;
-      const int ix1 = ix0 + (ix0 < g - 1 ? 1 : 0);
-      w1[p] = fminf(fmaxf(sx - (float)ix0, 0.f), 1.f);
-      w0[p] = 1.0f - w1[p];
+      int ix0, ix1;
+      bilinear_tap(scale, x, g, ix0, ix1, w0[p], w1[p]);
       o0[p] = ok[p] ? ix0 : 0;
       o1[p] = ok[p] ? ix1 : 0;
     }
@@ -270,10 +271,9 @@ __device__ __forceinline__ void blur_band(const float* grid, float* out, int b, 
     int cur0 = -1, cur1 = -1;
     for (int y = y0; y < y1; ++y) {
       // ATen upsample_bilinear2d, align_corners=True: src = scale * dst (fp32)
-      const float sy = scale * (float)y;
-      const int iy0 = (int)sy;
-      const int iy1 = iy0 + (iy0 < g - 1 ? 1 : 0);
-      const float hy1 = fminf(fmaxf(sy - (float)iy0, 0.f), 1.f), hy0 = 1.0f - hy1;
+      int iy0, iy1;
+      float hy0, hy1;
+      bilinear_tap(scale, y, g, iy0, iy1, hy0, hy1);
       if (iy0 != cur0) {
         if (iy0 == cur1) {
 #pragma unroll
@@ -296,20 +296,7 @@ __device__ __forceinline__ void blur_band(const float* grid, float* out, int b, 
         for (int p = 0; p < 8; ++p) v[c][p] = hy0 * H0[c][p] + hy1 * H1[c][p];
       if (C > 1 && softmax) {  // torch.softmax over the channel dim (forward_utils.py:214-215)
 #pragma unroll
-        for (int p = 0; p < 8; ++p) {
-          float m = v[0][p];
-#pragma unroll
-          for (int c = 1; c < C; ++c) m = fmaxf(m, v[c][p]);
-          float sum = 0.f;
-#pragma unroll
-          for (int c = 0; c < C; ++c) {
-            v[c][p] = expf(v[c][p] - m);
-            sum += v[c][p];
-          }
-          const float inv = 1.0f / sum;
-#pragma unroll
-          for (int c = 0; c < C; ++c) v[c][p] *= inv;
-        }
+        for (int p = 0; p < 8; ++p) softmax_channels<C, 8>(v, p);
       }
 #pragma unroll
       for (int c = 0; c < C; ++c) {
@@ -570,8 +557,22 @@ extern "C" int aaclip_patch_logits(int in_dtype, const void* f, int64_t ld, cons
   AACLIP_REQUIRE(f && T && out && rows >= 0 && channels == 768 && ld >= channels && ld % 4 == 0);
   AACLIP_REQUIRE(n_anchor >= 1 && n_anchor <= 64 && group > 0 && rows % group == 0);
   if (rows == 0) return AACLIP_OK;
-  patch_logits_kernel<<<ceil_div(rows, 4), 256, 0, (hipStream_t)stream>>>(in_dtype, f, ld, T, n_anchor, rows,
+  patch_logits_kernel<<<ceil_div(rows, 4), 256, 0, (hipStream_t)stream>>>(in_dtype, f, ld, T, 0, n_anchor, rows,
                                                                           group, out);
+  AACLIP_CHECK_LAUNCH();
+  return AACLIP_OK;
+}
+
+extern "C" int aaclip_patch_logits_per_image(int in_dtype, const void* f, int64_t ld, const float* T,
+                                             int64_t t_stride, int n_anchor, int rows, int channels, int group,
+                                             float* out, void* stream) {
+  AACLIP_REQUIRE(in_dtype == AACLIP_F32 || in_dtype == AACLIP_BF16);
+  AACLIP_REQUIRE(f && T && out && rows >= 0 && channels == 768 && ld >= channels && ld % 4 == 0);
+  AACLIP_REQUIRE(n_anchor >= 1 && n_anchor <= 8 && group > 0 && rows % group == 0);
+  AACLIP_REQUIRE(t_stride == 0 || t_stride >= (int64_t)channels * n_anchor);
+  if (rows == 0) return AACLIP_OK;
+  patch_logits_kernel<<<ceil_div(rows, 4), 256, 0, (hipStream_t)stream>>>(in_dtype, f, ld, T, t_stride, n_anchor,
+                                                                          rows, group, out);
   AACLIP_CHECK_LAUNCH();
   return AACLIP_OK;
 }

@@ -81,6 +81,39 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// ---------------------------------------------------------------- bilinear taps / channel softmax
+// ATen upsample_bilinear2d, align_corners=True, one axis: src = scale * dst in fp32
+// (scale = (g - 1) / (S - 1), rounded once on the host), rounded before the lambdas:
+// no FMA contraction. Shared by the forward (blur_band) and its backward
+// (upsample_softmax_bwd_kernel), so both put every pixel on the same source cells
+// with the same weights, bit for bit.
+__device__ __forceinline__ void bilinear_tap(float scale, int dst, int g, int& i0, int& i1, float& w0, float& w1) {
+#pragma clang fp contract(off)
+  const float s = scale * (float)dst;
+  i0 = (int)s;
+  i1 = i0 + (i0 < g - 1 ? 1 : 0);
+  w1 = fminf(fmaxf(s - (float)i0, 0.f), 1.f);
+  w0 = 1.0f - w1;
+}
+// torch.softmax over the C channels of pixel slot p, in place (max, exp, sum in channel
+// order, one reciprocal).
+template <int C, int N>
+__device__ __forceinline__ void softmax_channels(float (&v)[C][N], int p) {
+#pragma clang fp contract(off)
+  float m = v[0][p];
+#pragma unroll
+  for (int c = 1; c < C; ++c) m = fmaxf(m, v[c][p]);
+  float sum = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    v[c][p] = expf(v[c][p] - m);
+    sum += v[c][p];
+  }
+  const float inv = 1.0f / sum;
+#pragma unroll
+  for (int c = 0; c < C; ++c) v[c][p] *= inv;
+}
+
 // ---------------------------------------------------------------- launch checking
 #define AACLIP_CHECK_LAUNCH()                                 \
   do {                                                        \

@@ -6,14 +6,24 @@
       reduction in the aaclip_anchor_reduce kernel.
   calculate_similarity_map   forward_utils.py:196-216 — aaclip_patch_scores +
       aaclip_blur_upsample (test: (A1+1-A0)/2 -> Gaussian -> bilinear;
-      train: bilinear -> softmax over the two anchors).
+      train: bilinear -> softmax over the two anchors). The train branch also takes
+      the per-image [B, 768, Cn] anchors of train.py:69-72 and, for two anchors,
+      carries a backward to the anchors and the patch features
+      (aaclip_upsample_softmax_bwd -> aaclip_patch_logits_bwd).
+  calculate_seg_loss         forward_utils.py:219-227 — FocalLoss() + the two
+      BinaryDiceLoss() terms in aaclip_seg_loss, backward in aaclip_seg_loss_bwd.
+      With the map above this is train.py:86-100 from the anchors / features down
+      to loss.backward(). The text and image towers have no backward: encode_text
+      and get_adapted_*_text_embedding return tensors without a grad_fn, so the
+      anchors (or features) are the leaves.
   anomaly_map_multilevel     the fused form of test.py:86-93 (all levels in one
       stream kernel, level sum before blur+upsample).
   metrics_eval               forward_utils.py:233-280 — on device (aaclip_metrics_eval:
       min-max normalisation, score fusion, radix-sorted exact tie-aware AUROC / AP,
       identical to sklearn after the reference's 4-decimal rounding). numpy inputs
       are copied to the device; there is no CPU path (without a GPU it raises).
-Training losses and visualize() (cv2) are out of scope.
+FocalLoss / BinaryDiceLoss as classes with non-default arguments, the train data
+split and visualize() (cv2) are out of scope.
 """
 from __future__ import annotations
 
@@ -81,22 +91,76 @@ def get_adapted_text_embedding(model, dataset_name, device):
     return {c: T.to(device) for c, T in out.items()}
 
 
+class _TrainMap(torch.autograd.Function):
+    """Two-anchor train-branch map with a backward: grads flow to the patch features and /
+    or the anchors, whichever need them (aaclip_upsample_softmax_bwd -> aaclip_patch_logits_bwd)."""
+
+    @staticmethod
+    def forward(ctx, patch_features, epoch_text_feature, f, T, B, L, img_size):
+        H = int(np.sqrt(L))
+        grid = torch.empty(B, 2, H, H, device=f.device, dtype=torch.float32)
+        _train_logits(f, T, grid, L)
+        out = torch.empty(B, 2, img_size, img_size, device=f.device, dtype=torch.float32)
+        ops.blur_upsample(grid, out, ksize=0, sigma=0.0, softmax=True)
+        ctx.save_for_backward(f, T, grid)
+        ctx.L = L
+        ctx.f_meta = (patch_features.shape, patch_features.dtype)
+        ctx.t_meta = (epoch_text_feature.shape, epoch_text_feature.dtype, epoch_text_feature.device)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        f, T, grid = ctx.saved_tensors
+        need_df, need_dT = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        with torch.cuda.device(f.device):
+            dgrid = ops.upsample_softmax_bwd(grid, dout.to(torch.float32).contiguous())
+            dT, df = ops.patch_logits_bwd(f, T, dgrid, group=ctx.L, need_dT=need_dT, need_df=need_df)
+        if df is not None:
+            df = df.reshape(ctx.f_meta[0]).to(ctx.f_meta[1])
+        if dT is not None:
+            dT = dT.reshape(ctx.t_meta[0]).to(device=ctx.t_meta[2], dtype=ctx.t_meta[1])
+        return df, dT, None, None, None, None, None
+
+
+def _train_logits(f, T, grid, L):
+    """The train-branch logits launch: a shared anchor pair goes through patch_scores (mode 1),
+    any other shared count through patch_logits, per-image anchors through
+    patch_logits_per_image."""
+    if T.dim() == 3:
+        ops.patch_logits_per_image(f, T, grid, group=L)
+    elif T.shape[1] == 2:
+        ops.patch_scores([f], T, grid, normalize=False, mode=1, group=L)
+    else:  # any anchor count (reference forward_utils.py:199-215 handles every C)
+        ops.patch_logits(f, T, grid, group=L)
+
+
 def calculate_similarity_map(patch_features, epoch_text_feature, img_size, test=False, domain="Medical"):
-    """[B, L, C] features x [C, 2] anchors -> [B, 1, S, S] (test) / [B, 2, S, S] (train)."""
+    """[B, L, C] features x [C, 2] anchors -> [B, 1, S, S] (test) / [B, 2, S, S] (train).
+    The train branch also takes per-image anchors [B, C, Cn] (train.py:69-72); with two
+    anchors and a grad-requiring input its result has a backward."""
     B, L, C = patch_features.shape
     H = int(np.sqrt(L))
     if H * H != L:
         raise ValueError("patch count must be a square")
-    Cn = epoch_text_feature.shape[1]
+    if epoch_text_feature.dim() not in (2, 3) or (test and epoch_text_feature.dim() != 2):
+        raise ValueError("anchors must be [C, Cn]" + ("" if test else " or per image [B, C, Cn]"))
+    if epoch_text_feature.dim() == 3 and epoch_text_feature.shape[0] != B:
+        raise ValueError(f"per-image anchors need one set per image: got {epoch_text_feature.shape[0]} for {B}")
+    Cn = epoch_text_feature.shape[-1]
     if test:
         assert Cn == 2
     elif not 1 <= Cn <= 8:  # checked before any launch: the train-branch upsample holds <= 8 channels per pixel
         raise ValueError(f"train-branch similarity map supports 1..8 anchors, got {Cn}")
-    f = patch_features.reshape(B * L, C)
+    wants_grad = not test and torch.is_grad_enabled() and (patch_features.requires_grad
+                                                           or epoch_text_feature.requires_grad)
+    if wants_grad and Cn != 2:
+        raise NotImplementedError(f"the train-branch backward is written for 2 anchors, got {Cn}")
+    f = patch_features.detach().reshape(B * L, C)
     if f.dtype not in (torch.float32, torch.bfloat16):
         f = f.float()
     f = f.contiguous()
-    T = epoch_text_feature.to(f.device, torch.float32).contiguous()
+    T = epoch_text_feature.detach().to(f.device, torch.float32).contiguous()
     dev = f.device
     if test:
         grid = torch.empty(B, 1, H, H, device=dev, dtype=torch.float32)
@@ -104,13 +168,54 @@ def calculate_similarity_map(patch_features, epoch_text_feature, img_size, test=
         k, s = _blur_for(domain)
         out = torch.empty(B, 1, img_size, img_size, device=dev, dtype=torch.float32)
         return ops.blur_upsample(grid, out, ksize=k, sigma=s)
+    if wants_grad:
+        return _TrainMap.apply(patch_features, epoch_text_feature, f, T, B, L, img_size)
     grid = torch.empty(B, Cn, H, H, device=dev, dtype=torch.float32)
-    if Cn == 2:
-        ops.patch_scores([f], T, grid, normalize=False, mode=1, group=L)
-    else:  # any anchor count (reference forward_utils.py:199-215 handles every C)
-        ops.patch_logits(f, T, grid, group=L)
+    _train_logits(f, T, grid, L)
     out = torch.empty(B, Cn, img_size, img_size, device=dev, dtype=torch.float32)
     return ops.blur_upsample(grid, out, ksize=0, sigma=0.0, softmax=Cn > 1)
+
+
+class _SegLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, patch_preds, probs, mask):
+        sums, loss = ops.seg_loss(probs, mask)
+        ctx.save_for_backward(probs, mask, sums)
+        ctx.meta = (patch_preds.shape, patch_preds.dtype)
+        return loss[3].clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dloss):
+        probs, mask, sums = ctx.saved_tensors
+        with torch.cuda.device(probs.device):
+            dloss = dloss.to(probs.device, torch.float32).reshape(1).contiguous()
+            dprobs = ops.seg_loss_bwd(probs, mask, sums, dloss)
+        return dprobs.reshape(ctx.meta[0]).to(ctx.meta[1]), None, None
+
+
+def calculate_seg_loss(patch_preds, mask):
+    """forward_utils.py:219-227: FocalLoss()(patch_preds, mask) + BinaryDiceLoss()(patch_preds[:, 0],
+    1 - mask) + BinaryDiceLoss()(patch_preds[:, 1], mask) as one device pass (aaclip_seg_loss), with
+    a backward to patch_preds (aaclip_seg_loss_bwd). patch_preds [B, 2, S, S]; mask [B, 1, S, S] or
+    [B, S, S], any float dtype, values in [0, 1] (outside that the reference's scatter_ raises; here
+    it is undefined). Returns a 0-dim fp32 device tensor."""
+    if patch_preds.dim() != 4 or patch_preds.shape[1] != 2 or patch_preds.shape[2] != patch_preds.shape[3]:
+        raise ValueError("patch_preds must be [B, 2, S, S]")
+    if not patch_preds.is_cuda:
+        raise RuntimeError("calculate_seg_loss runs on the MI355X kernels (aaclip_seg_loss); it needs device "
+                           "tensors and there is no CPU path")
+    B, _, S, _ = patch_preds.shape
+    if mask.dim() == 4 and mask.shape[1] == 1:
+        mask = mask[:, 0]
+    if tuple(mask.shape) != (B, S, S) or not mask.is_floating_point():
+        raise ValueError(f"mask must be a float [B, 1, S, S] or [B, S, S] matching patch_preds, got {tuple(mask.shape)}")
+    mask = mask.detach().to(patch_preds.device, torch.float32).contiguous()
+    probs = patch_preds.detach().to(torch.float32).contiguous()
+    with torch.cuda.device(patch_preds.device):
+        if torch.is_grad_enabled() and patch_preds.requires_grad:
+            return _SegLoss.apply(patch_preds, probs, mask)
+        return ops.seg_loss(probs, mask)[1][3].clone()
 
 
 def anomaly_map_multilevel(patch_features, epoch_text_feature, img_size, domain="Industrial", normalize=False):

@@ -51,7 +51,12 @@ extern "C" {
 
 /* ABI version (bumped on any signature change; 2 = MX fp8 LayerNorm outputs, 3 = fp16 dtype,
  * aaclip_patch_logits, any-size blur_upsample; 6 = round 5: the rejected A/B entry points
- * removed, aaclip_trace_buffer added; 8 = aaclip_vv_attention) and the target. */
+ * removed, aaclip_trace_buffer added; 8 = aaclip_vv_attention) and the target.
+ * The stage-1 loss head (aaclip_patch_logits_per_image, aaclip_seg_loss, aaclip_seg_loss_bwd,
+ * aaclip_upsample_softmax_bwd, aaclip_patch_logits_bwd, aaclip_patch_logits_bwd_workspace)
+ * was added under version 8: additions only, no existing signature changed. A version-8
+ * library built before them is still refused by the loader, which checks that every
+ * symbol it binds is exported ("lacks ...: stale"). */
 int aaclip_abi_version(void);
 const char* aaclip_arch(void);
 
@@ -371,6 +376,16 @@ int aaclip_patch_logits(int in_dtype, const void* f, int64_t ld, const float* T,
                         int rows, int channels, int group, float* out, void* stream);
 
 /*
+ * aaclip_patch_logits with per-image anchors: the anchors of image b = row / group are at
+ * T + b * t_stride floats ([channels, n_anchor] each; t_stride == 0: one shared set, and
+ * then the output is bit-identical to aaclip_patch_logits, the same kernel). 1 <= n_anchor
+ * <= 8 (what aaclip_blur_upsample takes), t_stride == 0 or >= channels * n_anchor.
+ * Replaces: forward_utils.py:199-202 on the [bs, 768, 2] anchors of train.py:69-72, :86-89.
+ */
+int aaclip_patch_logits_per_image(int in_dtype, const void* f, int64_t ld, const float* T, int64_t t_stride,
+                                  int n_anchor, int rows, int channels, int group, float* out, void* stream);
+
+/*
  * Gaussian blur (kornia 0.6.9 gaussian_blur2d, reflect border, separable;
  * skipped when ksize == 0) then bilinear upsample with align_corners=True
  * (F.interpolate) to any out_size, optional softmax over the channel dim
@@ -380,6 +395,68 @@ int aaclip_patch_logits(int in_dtype, const void* f, int64_t ld, const float* T,
  */
 int aaclip_blur_upsample(const float* grid, float* out, int batch, int channels, int g,
                          int out_size, int ksize, float sigma, int softmax, void* stream);
+
+/*
+ * Stage-1 segmentation loss, forward: FocalLoss() + BinaryDiceLoss()(p0, 1 - mask) +
+ * BinaryDiceLoss()(p1, mask) as forward_utils.py:219-227 constructs them (:21-126).
+ * probs [batch, 2, S, S] fp32 (S = out_size >= 2), mask [batch, S, S] fp32 in [0, 1].
+ * Per pixel k = (int)mask, o_k = 1 - 1e-5, o_other = 1e-5, pt = o_0 p0 + o_1 p1 + 1e-5,
+ * term = -(1 - pt)^2 log(pt); t_0 = 1 - mask, t_1 = mask.
+ * sums [batch][8] fp64 = {sum term, sum p0 t0, sum p0, sum t0, sum p1 t1, sum p1, sum t1, 0}
+ * per image (each depends on that image alone); loss[4] fp32 = {focal, dice0, dice1,
+ * (focal + dice0) + dice1}, focal = sum term / (batch S^2), dice_c = 1 - (1/batch) sum_n
+ * (2 sum p_c t_c + 1) / (sum p_c + sum t_c + 1).
+ * partial: caller-owned workspace of >= batch * ceil(S^2 / AACLIP_SEGLOSS_CHUNK) * 8 doubles
+ * (partial_bytes is checked). fp32 per pixel, fixed-order sums (fp64 across waves and
+ * chunks), no atomics: two launches give the same bits. Replaces: calculate_seg_loss in the
+ * stage-1 step train.py:86-100 (:90).
+ */
+#define AACLIP_SEGLOSS_CHUNK 4096
+int aaclip_seg_loss(const float* probs, const float* mask, int batch, int out_size, double* partial,
+                    size_t partial_bytes, double* sums, float* loss, void* stream);
+
+/*
+ * Backward of aaclip_seg_loss: dprobs [batch, 2, S, S] = dloss * d loss[3] / d probs, from
+ * probs, mask, the sums aaclip_seg_loss wrote and the DEVICE scalar dloss (autograd's
+ * grad_output; no host read). d focal / d p_c = o_c (2 (1 - pt) log pt - (1 - pt)^2 / pt) /
+ * (batch S^2); d dice_c / d p_c = -(2 t_c D - Nn) / (batch D^2) with the image's
+ * Nn = 2 sum p_c t_c + 1, D = sum p_c + sum t_c + 1. The mask gets no gradient.
+ * Replaces: the autograd of forward_utils.py:21-126, :219-227 under train.py:96.
+ */
+int aaclip_seg_loss_bwd(const float* probs, const float* mask, const double* sums, const float* dloss,
+                        int batch, int out_size, float* dprobs, void* stream);
+
+/*
+ * Backward of aaclip_blur_upsample(ksize = 0, softmax = 1) for channels == 2: grid
+ * [batch, 2, g, g] (the logits the forward consumed; 2 <= g <= 64) and dprobs
+ * [batch, 2, S, S] -> dgrid [batch, 2, g, g]. Each pixel's two probabilities are
+ * recomputed from grid with the forward's arithmetic (the same device functions), softmax
+ * backward dz_c = p_c (g_c - sum_k p_k g_k) (evaluated as p_0 p_1 (g_c - g_other), which does
+ * not lean on p_0 + p_1 == 1 in fp32), then the transpose of the align_corners
+ * bilinear interpolation as a gather (one wave per source cell; a pixel belongs to a cell
+ * iff the forward's index computation puts it there). No atomics, deterministic.
+ * Replaces: the autograd of forward_utils.py:211-215 under train.py:96.
+ */
+int aaclip_upsample_softmax_bwd(const float* grid, const float* dprobs, int batch, int channels, int g,
+                                int out_size, float* dgrid, void* stream);
+
+/*
+ * Backward of the train-branch logits out[b, a, p] = 100 f[b group + p] . T_b[:, a]
+ * (n_anchor == 2; f [rows, channels == 768] fp32/bf16, T_b at T + b * t_stride as in
+ * aaclip_patch_logits_per_image, dgrid [batch, 2, group]). Either output may be NULL:
+ *   dT[b, c, a] = 100 sum_p f[b group + p, c] dgrid[b, a, p]   ([batch, 768, 2] fp32; with
+ *                 t_stride == 0 summed over the images in index order into one [768, 2])
+ *   df[row, c]  = 100 sum_a dgrid[b, a, p] T_b[c, a]           ([rows, 768] fp32, contiguous)
+ * f is read once: one wave per (image, AACLIP_LOGITS_BWD_ROWS patch rows) writes a dT
+ * partial into workspace (needed when dT != NULL; aaclip_patch_logits_bwd_workspace gives
+ * its size in bytes), a finalize pass sums the chunks in index order in fp64.
+ * Replaces: the autograd of forward_utils.py:199-202 under train.py:96.
+ */
+#define AACLIP_LOGITS_BWD_ROWS 16
+int aaclip_patch_logits_bwd_workspace(int rows, int group, size_t* bytes);
+int aaclip_patch_logits_bwd(int in_dtype, const void* f, int64_t ld, const float* T, int64_t t_stride,
+                            int n_anchor, const float* dgrid, int rows, int channels, int group,
+                            float* workspace, size_t workspace_bytes, float* dT, float* df, void* stream);
 
 /*
  * Full test-branch anomaly map for one batch: patch_scores (mode 0) into the
