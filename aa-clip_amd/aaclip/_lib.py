@@ -70,6 +70,15 @@ SIGNATURES = {
     "aaclip_upsample_softmax_bwd": [_P, _P, _I, _I, _I, _I, _P, _P],
     "aaclip_patch_logits_bwd_workspace": [_I, _I, ctypes.POINTER(ctypes.c_size_t)],
     "aaclip_patch_logits_bwd": [_I, _P, _L, _P, _L, _I, _P, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P],
+    "aaclip_attention_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "aaclip_layernorm_bwd": [_P, _L, _P, _L, _P, _P, _L, _P, _L, _I, _I, _P],
+    "aaclip_eot_ln_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "aaclip_act": [_I, _P, _P, _L, _P],
+    "aaclip_act_bwd": [_I, _P, _P, _P, _L, _P],
+    "aaclip_adapter_blend_bwd": [_P, _P, _P, _F, _P, _P, _I, _I, _P],
+    "aaclip_anchor_reduce_bwd": [_P, _I, _I, _P, _I, _I, _P, _P],
+    "aaclip_linear_wgrad_workspace": [_I, _I, _I, ctypes.POINTER(ctypes.c_size_t)],
+    "aaclip_linear_wgrad": [_P, _L, _P, _L, _I, _I, _I, _P, ctypes.c_size_t, _P, _L, _P],
     "aaclip_anomaly_map": [_I, _P, _I, _L, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P],
     "aaclip_image_score": [_I, _P, _L, _P, _I, _I, _I, _I, _P, _P, _P, _P],
     "aaclip_metrics_workspace": [_L, _I, ctypes.POINTER(ctypes.c_size_t)],

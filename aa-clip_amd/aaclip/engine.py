@@ -3,7 +3,9 @@
 VisualEngine = AdaptedCLIP.forward (reference model/adapter.py:67-112) +
 the anomaly map / image score of test.py:80-93; TextEngine =
 AdaptedCLIP.encode_text / CLIP.encode_text (adapter.py:114-145,
-model/model.py:190-201) + the prompt-ensemble anchors (forward_utils.py:138-162).
+model/model.py:190-201) + the prompt-ensemble anchors (forward_utils.py:138-162), and
+TextEngine.encode_train, the same forward with a HIP backward into the text adapter
+weights (stage 1, train.py:38-114).
 
 Data layout in HBM (token-major "NLD", one row per token):
   x      fp32 [B*(P+1), 1024]   residual stream (kept fp32 across all 24 blocks)
@@ -603,13 +605,27 @@ class TextEngine:
             ))
         self.adapted = text_adapter is not None
         self.t_w = float(text_adapt_weight)
+        self._bwd = None  # transposed frozen weights for the input-gradient GEMMs (encode_train)
+        # tests / debugging: blocks whose output gradient [R, width] each backward appends to
+        # tap_records as {"n", "ctx", "taps": {block: tensor}} (empty: nothing is kept)
+        self.tap_blocks, self.tap_records = (), []
         if self.adapted:
             self.adapt_until = int(text_adapt_until)
-            self.w_adapt = [cdt(text_adapter[f"{i}.fc.0.weight"]) for i in range(self.adapt_until)]
-            self.w_out = cdt(text_adapter[f"{self.adapt_until}.fc.0.weight"])  # Linear + LeakyReLU
+            self.set_adapter(text_adapter)
         else:
             self.adapt_until = 0
             self.w_out = cdt(params["text_projection"].t())  # x @ P == x . (P^T)^T
+
+    def set_adapter(self, text_adapter: dict):
+        """(Re)bind the adapter weights encode() reads: adapt_until SimpleAdapters + the output
+        SimpleProj (Linear + LeakyReLU). The frozen packing (block weights, their transposes,
+        the token embedding) is untouched, so an optimizer step costs no repacking; fp32
+        device parameters are referenced, not copied."""
+        if not self.adapted:
+            raise RuntimeError("this TextEngine was built without a text adapter")
+        cdt = lambda t: t.detach().to(self.device, self.dtype).contiguous()  # noqa: E731
+        self.w_adapt = [cdt(text_adapter[f"{i}.fc.0.weight"]) for i in range(self.adapt_until)]
+        self.w_out = cdt(text_adapter[f"{self.adapt_until}.fc.0.weight"])  # Linear + LeakyReLU
 
     @torch.no_grad()
     @_on_device
@@ -662,6 +678,171 @@ class TextEngine:
         for col, tok in enumerate((tok_normal, tok_abnormal)):
             ops.anchor_reduce(self.encode(tok), T, col)
         return T
+
+    # ------------------------------------------------------------------ training (stage 1)
+    def _bwd_weights(self):
+        """W^T copies of the frozen block weights: dX = dY . W is aaclip_gemm (C = A . W'^T)
+        with W' = W^T. Packed once per engine, on the first training call; block 0 never
+        needs a backward (no trainable weight lies below the adapter that follows it)."""
+        if self._bwd is None:
+            tr = lambda w: w.t().contiguous()  # noqa: E731
+            self._bwd = [None] + [dict(w_qkv=tr(b["w_qkv"]), w_o=tr(b["w_o"]), w_fc=tr(b["w_fc"]), w_pr=tr(b["w_pr"]))
+                                  for b in self.blocks[1:]]
+        return self._bwd
+
+    def encode_train(self, tokens: torch.Tensor, adapter_weights, truncate: bool = True) -> torch.Tensor:
+        """encode() with a grad_fn into the text adapter: adapter_weights are the adapt_until
+        SimpleAdapter weights followed by the output SimpleProj weight ([width, width] ...,
+        [embed, width]; fp32 tensors on this engine's device, normally the live nn.Parameters),
+        read as they are at the call. The embeddings are bit-identical to encode()'s on the
+        same weights; backward fills .grad of the weights that require it and computes nothing
+        for the frozen tower."""
+        if not self.adapted:
+            raise RuntimeError("encode_train needs an engine built with a text adapter")
+        if self.dtype != torch.float32:
+            raise RuntimeError("the text tower trains in fp32 only")
+        ws = list(adapter_weights)
+        if len(ws) != self.adapt_until + 1:
+            raise ValueError(f"expected {self.adapt_until + 1} adapter weights, got {len(ws)}")
+        W = self.width
+        for i, w in enumerate(ws):
+            want = (W, W) if i < self.adapt_until else (self.w_out.shape[0], W)
+            if w.device != self.device or w.dtype != torch.float32 or tuple(w.shape) != want or not w.is_contiguous():
+                raise ValueError(f"adapter weight {i} must be a contiguous fp32 {list(want)} tensor on {self.device}")
+        if tokens.dim() != 2 or tokens.shape[1] != self.pos.shape[0]:
+            raise ValueError("token context length mismatch")
+        return _TextTrain.apply(self, tokens, bool(truncate), *ws)
+
+    @_on_device
+    def _train_forward(self, tokens, truncate, ws, lowest):
+        """The launches of encode(), with c_fc's pre-activation kept (aaclip_gemm bias-only +
+        aaclip_act: the epilogue's own device function) and every block from `lowest` + 1 up
+        writing fresh buffers. lowest = index of the lowest adapter that needs a gradient
+        (None: only the output projection trains, nothing below the EOT rows is kept)."""
+        n, ctx = tokens.shape
+        if truncate and n > 0:
+            ctx = int(tokens.argmax(-1).max()) + 1
+            tokens = tokens[:, :ctx]
+        tokens = tokens.to(self.device, torch.int32).contiguous()
+        R, W = n * ctx, self.width
+        dev = self.device
+        e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
+        X, H = e(R, W), e(R, W)
+        qkv, att, fc = e(R, 3 * W), e(R, W), e(R, 4 * W)
+        fc_pre, u = fc, e(R, W)
+        ops.text_embed_ln(tokens, self.tok_emb, self.pos, self.blocks[0]["ln1"], X, H)
+        nb = len(self.blocks)
+        saved = {}
+        for i, blk in enumerate(self.blocks):
+            keep = lowest is not None and i > lowest        # this block has a backward
+            adapt = i < self.adapt_until
+            keep_blend = lowest is not None and adapt and i >= lowest
+            if keep:
+                qkv, fc_pre = e(R, 3 * W), e(R, 4 * W)
+            ops.gemm(H, blk["w_qkv"], qkv, bias=blk["b_qkv"])
+            ops.attention(qkv, att, n, ctx, self.heads, causal=True)
+            x_in = X
+            x_mid = e(R, W) if keep else X
+            ops.gemm(att, blk["w_o"], x_mid, bias=blk["b_o"], residual=x_in)
+            ops.layernorm(x_mid, blk["ln2"][0], blk["ln2"][1], H)
+            if keep:
+                ops.gemm(H, blk["w_fc"], fc_pre, bias=blk["b_fc"])
+                ops.act(fc_pre, self.act, out=fc)
+            else:
+                ops.gemm(H, blk["w_fc"], fc, bias=blk["b_fc"], gelu=self.act)
+            X = e(R, W) if (keep or keep_blend) else x_mid
+            ops.gemm(fc, blk["w_pr"], X, bias=blk["b_pr"], residual=x_mid)
+            if keep:
+                saved[i] = dict(x_in=x_in, qkv=qkv, x_mid=x_mid, fc_pre=fc_pre)
+            nxt = self.blocks[i + 1]["ln1"] if i + 1 < nb else None
+            if adapt:
+                if keep_blend:
+                    u = e(R, W)
+                ops.gemm(X, ws[i], u, leaky=True)
+                if keep_blend:  # the blend is in place: keep the pre-blend x, blend a copy
+                    saved.setdefault(i, {}).update(x_pre=X, u=u)
+                    X = X.clone()
+                ops.block_tail(X, ctx, u=u, adapt_weight=self.t_w, ln=nxt, h=H if nxt else None)
+            elif nxt is not None:
+                ops.layernorm(X, nxt[0], nxt[1], H)
+        eot = e(n, W)
+        ops.eot_ln(X, tokens, self.ln_final, eot)
+        out = e(n, ws[-1].shape[0])
+        ops.gemm(eot, ws[-1], out, leaky=True)
+        return out, dict(tokens=tokens, n=n, ctx=ctx, blocks=saved, x_final=X if lowest is not None else None,
+                         eot=eot, lowest=lowest)
+
+    @_on_device
+    def _train_backward(self, st, ws, need, demb):
+        """Gradients of the adapter weights `need` marks, from demb = dL/d(embeddings)."""
+        n, ctx, tokens, lowest = st["n"], st["ctx"], st["tokens"], st["lowest"]
+        R, W = n * ctx, self.width
+        dev = self.device
+        e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
+        grads = [None] * len(ws)
+        # out = LeakyReLU(eot W_out^T)
+        d_o = ops.act_bwd(demb, st["out"], "leaky")
+        if need[-1]:
+            grads[-1] = ops.linear_wgrad(d_o, st["eot"])
+        if lowest is None:
+            return grads
+        bw = self._bwd_weights()
+        d_eot = ops.gemm(d_o, ws[-1].detach().t().contiguous(), e(n, W))
+        g = ops.eot_ln_bwd(d_eot, st["x_final"], tokens, self.ln_final[0])
+        d_qkv, d_wide, d_w, du = e(R, 3 * W), e(R, 4 * W), e(R, W), e(R, W)
+        act_mode = "quick" if self.act == "quick" else "gelu"
+        taps = {}
+        for i in range(len(self.blocks) - 1, lowest - 1, -1):
+            sv = st["blocks"].get(i, {})
+            if "u" in sv:  # x <- w u |x| / |u| + (1 - w) x after block i, u = LeakyReLU(x Wa_i^T)
+                ops.adapter_blend_bwd(g, sv["x_pre"], sv["u"], self.t_w, dx=g, du=du)
+                ops.act_bwd(du, sv["u"], "leaky", out=du)
+                if need[i]:
+                    grads[i] = ops.linear_wgrad(du, sv["x_pre"])
+                if i > lowest:
+                    ops.gemm(du, ws[i].detach().t().contiguous(), g, residual=g)
+            if i in self.tap_blocks:  # diagnostic: dL/d(block i's own output), the adapter path included
+                taps[i] = g.clone() if i > lowest else ops.gemm(du, ws[i].detach().t().contiguous(), e(R, W),
+                                                                residual=g)
+            if i == lowest:
+                break
+            blk, bt = self.blocks[i], bw[i]
+            ops.gemm(g, bt["w_pr"], d_wide)                                    # 1. d_act = g . W_pr
+            ops.act_bwd(d_wide, sv["fc_pre"], act_mode, out=d_wide)            # 2. d_pre = d_act gelu'(fc_pre)
+            ops.gemm(d_wide, bt["w_fc"], d_w)                                  # 3. d_h2 = d_pre . W_fc
+            ops.layernorm_bwd(d_w, sv["x_mid"], blk["ln2"][0], residual=g, out=g)  # 4. g_mid
+            ops.gemm(g, bt["w_o"], d_w)                                        # 5. d_att = g_mid . W_o
+            ops.attention_bwd(sv["qkv"], d_w, n, ctx, self.heads, causal=True, dqkv=d_qkv)  # 6.
+            ops.gemm(d_qkv, bt["w_qkv"], d_w)                                  # 7. d_h1 = d_qkv . W_qkv
+            ops.layernorm_bwd(d_w, sv["x_in"], blk["ln1"][0], residual=g, out=g)   # 8. g_in
+        if self.tap_blocks:
+            self.tap_records.append(dict(n=n, ctx=ctx, taps=taps))
+        return grads
+
+
+class _TextTrain(torch.autograd.Function):
+    """TextEngine.encode with a backward into the text adapter weights (stage 1)."""
+
+    @staticmethod
+    def forward(ctx, engine, tokens, truncate, *ws):
+        need = ctx.needs_input_grad[3:]
+        low = [i for i in range(engine.adapt_until) if need[i]]
+        dws = [w.detach() for w in ws]
+        out, st = engine._train_forward(tokens, truncate, dws, low[0] if low else None)
+        ctx.engine, ctx.st = engine, st
+        ctx.save_for_backward(*ws, out)  # the output (LeakyReLU's backward reads it) goes through autograd
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, demb):
+        *ws, out = ctx.saved_tensors
+        need = list(ctx.needs_input_grad[3:])
+        eng = ctx.engine
+        demb = demb.to(eng.device, torch.float32).contiguous()
+        grads = eng._train_backward(dict(ctx.st, out=out), [w.detach() for w in ws], need, demb)
+        ctx.st = None
+        return (None, None, None, *grads)
 
 
 class FrozenVisualEngine:

@@ -731,6 +731,241 @@ def patch_logits_bwd(f, T, dgrid, *, group, need_dT=True, need_df=True, workspac
     return dT, df
 
 
+# ------------------------------------------------------------------------ text-tower backward
+WGRAD_ROWS = 64     # AACLIP_WGRAD_ROWS
+ATTN_BWD_MAX_SEQ = 77
+_ACT_MODES = {"gelu": _lib.EPI_GELU, True: _lib.EPI_GELU, "quick": _lib.EPI_QGELU, "leaky": _lib.EPI_LEAKY}
+
+
+def _f32rows(t, name, shape=None):
+    """fp32, 2-D, unit column stride, 16-byte aligned rows (the row kernels move float4)."""
+    _rowmajor(t, name)
+    if t.dtype != torch.float32 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{name} must be fp32" + (f" {list(shape)}" if shape is not None else ""))
+    if t.stride(0) % 4 or t.data_ptr() % 16:
+        raise ValueError(f"{name}: row stride must be a multiple of 4 and the start 16-byte aligned")
+
+
+def _act_mode(mode):
+    try:
+        return _ACT_MODES[mode]
+    except (KeyError, TypeError):
+        raise ValueError("activation mode must be 'gelu' (or True), 'quick' or 'leaky'") from None
+
+
+def attention_bwd(qkv, dout, batch: int, seq: int, heads: int, *, causal: bool = False, dqkv=None):
+    """dqkv [batch*seq, 3*heads*64] of the fp32 attention core from its packed qkv and dout
+    [batch*seq, heads*64]; seq <= 77 (the text context)."""
+    hd = 64
+    if not 1 <= seq <= ATTN_BWD_MAX_SEQ:
+        raise ValueError(f"attention_bwd holds one sequence in LDS: seq must be 1..{ATTN_BWD_MAX_SEQ}, got {seq}")
+    if batch < 1 or heads < 1:
+        raise ValueError("attention_bwd needs batch >= 1 and heads >= 1")
+    _f32c(qkv, "qkv", (batch * seq, 3 * heads * hd))
+    _f32c(dout, "dout", (batch * seq, heads * hd))
+    if dqkv is None:
+        dqkv = torch.empty_like(qkv)
+    _f32c(dqkv, "dqkv", qkv.shape)
+    if dqkv.data_ptr() == qkv.data_ptr():
+        raise ValueError("attention_bwd: dqkv must not alias qkv")
+    _dev(qkv, dout, dqkv)  # after the shape / dtype checks: those need no device
+    _launch("text_bwd", "attention_bwd", 10.0 * batch * heads * seq * seq * hd / (2 if causal else 1),
+            (2 * qkv.numel() + dout.numel()) * 4, "aaclip_attention_bwd", _ptr(qkv), _ptr(dout), _ptr(dqkv), batch,
+            seq, heads, hd, _lib.ATTN_CAUSAL if causal else 0, _stream())
+    return dqkv
+
+
+def layernorm_bwd(dy, x, w, *, residual=None, out=None):
+    """out = [residual +] LN_bwd(dy; x, w) per row (no dw / db); residual and dy may be out."""
+    _f32rows(x, "x")
+    rows, width = x.shape
+    if width not in (768, 1024):
+        raise ValueError("layernorm_bwd supports widths 768 and 1024")
+    _f32rows(dy, "dy", x.shape)
+    if w.dtype != torch.float32 or tuple(w.shape) != (width,) or not w.is_contiguous() or w.data_ptr() % 16:
+        raise ValueError("w must be contiguous fp32 [width]")
+    if residual is not None:
+        _f32rows(residual, "residual", x.shape)
+    if out is None:
+        out = torch.empty(rows, width, device=x.device, dtype=torch.float32)
+    _f32rows(out, "out", x.shape)
+    if out.data_ptr() == x.data_ptr():
+        raise ValueError("layernorm_bwd: out must not alias x")
+    for t, n in ((dy, "dy"), (residual, "residual")):
+        if t is not None and t.data_ptr() == out.data_ptr() and t.stride(0) != out.stride(0):
+            raise ValueError(f"layernorm_bwd: {n} aliases out with another row stride")
+    _dev(dy, x, w, residual, out)  # after the shape / dtype checks: those need no device
+    _launch("text_bwd", "layernorm_bwd", 0.0, rows * width * 4 * (4 if residual is not None else 3),
+            "aaclip_layernorm_bwd", _ptr(dy), dy.stride(0), _ptr(x), x.stride(0), _ptr(w), _ptr(residual),
+            0 if residual is None else residual.stride(0), _ptr(out), out.stride(0), rows, width, _stream())
+    return out
+
+
+def eot_ln_bwd(dy, x, tokens, w, *, out=None):
+    """g [n*ctx, width]: the ln_final backward of dy [n, width] at each sequence's EOT row, 0 elsewhere."""
+    if tokens.dim() != 2 or tokens.dtype != torch.int32 or not tokens.is_contiguous():
+        raise ValueError("tokens must be contiguous int32 [n, ctx]")
+    n, ctx = tokens.shape
+    if n < 1 or ctx < 1:
+        raise ValueError("eot_ln_bwd needs at least one sequence and one token")
+    if x.dim() != 2 or x.shape[0] != n * ctx or x.shape[1] not in (768, 1024):
+        raise ValueError("x must be [n*ctx, width] with width 768 or 1024")
+    width = x.shape[1]
+    _f32c(x, "x")
+    _f32c(dy, "dy", (n, width))
+    _f32c(w, "w", (width,))
+    if out is None:
+        out = torch.empty_like(x)
+    _f32c(out, "out", x.shape)
+    if out.data_ptr() in (x.data_ptr(), dy.data_ptr()):
+        raise ValueError("eot_ln_bwd: out must not alias x or dy")
+    for t, nm in ((x, "x"), (dy, "dy"), (w, "w"), (out, "out")):
+        if t.data_ptr() % 16:
+            raise ValueError(f"eot_ln_bwd: {nm} must be 16-byte aligned")
+    _dev(dy, x, tokens, w, out)  # after the shape / dtype checks: those need no device
+    _launch("text_bwd", "eot_ln_bwd", 0.0, (x.numel() + 2 * n * width) * 4, "aaclip_eot_ln_bwd", _ptr(dy), _ptr(x),
+            _ptr(tokens), _ptr(w), _ptr(out), n, ctx, width, _stream())
+    return out
+
+
+def act(x, mode, *, out=None):
+    """out = f(x), f = the fp32 GEMM epilogue's own 'gelu' / 'quick' / 'leaky' (out may be x)."""
+    m = _act_mode(mode)
+    _f32c(x, "x")
+    if out is None:
+        out = torch.empty_like(x)
+    _f32c(out, "out", x.shape)
+    _dev(x, out)  # after the shape / dtype checks: those need no device
+    _launch("text_bwd", "act", 0.0, 8.0 * x.numel(), "aaclip_act", m, _ptr(x), _ptr(out), x.numel(), _stream())
+    return out
+
+
+def act_bwd(dy, ref, mode, *, out=None):
+    """out = dy * f'(.): ref is the pre-activation for 'gelu' / 'quick', the OUTPUT for 'leaky'."""
+    m = _act_mode(mode)
+    _f32c(dy, "dy")
+    _f32c(ref, "ref", dy.shape)
+    if out is None:
+        out = torch.empty_like(dy)
+    _f32c(out, "out", dy.shape)
+    _dev(dy, ref, out)  # after the shape / dtype checks: those need no device
+    _launch("text_bwd", "act_bwd", 0.0, 12.0 * dy.numel(), "aaclip_act_bwd", m, _ptr(dy), _ptr(ref), _ptr(out),
+            dy.numel(), _stream())
+    return out
+
+
+def adapter_blend_bwd(dy, x, u, adapt_weight: float, *, dx=None, du=None):
+    """(dx, du) of y = w u |x| / |u| + (1 - w) x; dx is the path through x alone and may be dy."""
+    if x.dim() != 2 or x.shape[1] not in (768, 1024):
+        raise ValueError("adapter_blend_bwd takes [rows, 768 | 1024] tensors")
+    _f32c(x, "x")
+    _f32c(dy, "dy", x.shape)
+    _f32c(u, "u", x.shape)
+    if dx is None:
+        dx = torch.empty_like(x)
+    if du is None:
+        du = torch.empty_like(x)
+    _f32c(dx, "dx", x.shape)
+    _f32c(du, "du", x.shape)
+    if dx.data_ptr() in (x.data_ptr(), u.data_ptr()) or \
+            du.data_ptr() in (x.data_ptr(), u.data_ptr(), dy.data_ptr(), dx.data_ptr()):
+        raise ValueError("adapter_blend_bwd: only dx may alias an input (dy)")
+    for t in (dy, x, u, dx, du):
+        if t.data_ptr() % 16:
+            raise ValueError("adapter_blend_bwd operands must be 16-byte aligned")
+    _dev(dy, x, u, dx, du)  # after the shape / dtype checks: those need no device
+    _launch("text_bwd", "adapter_blend_bwd", 0.0, 20.0 * x.numel(), "aaclip_adapter_blend_bwd", _ptr(dy), _ptr(x),
+            _ptr(u), float(adapt_weight), _ptr(dx), _ptr(du), x.shape[0], x.shape[1], _stream())
+    return dx, du
+
+
+def anchor_reduce_bwd(emb, dT, col: int, *, out=None):
+    """demb [n, dim] from dT[:, col] through normalize(mean_s normalize(emb[s]))."""
+    if emb.dim() != 2 or not 1 <= emb.shape[0] <= 256 or not 1 <= emb.shape[1] <= 1024:
+        raise ValueError("emb must be [n <= 256, dim <= 1024]")
+    _f32c(emb, "emb")
+    n, dim = emb.shape
+    if dT.dim() != 2 or dT.shape[0] != dim or not 0 <= col < dT.shape[1]:
+        raise ValueError("dT must be [dim, ncols] with 0 <= col < ncols")
+    _f32c(dT, "dT")
+    if out is None:
+        out = torch.empty_like(emb)
+    _f32c(out, "out", emb.shape)
+    if out.data_ptr() == emb.data_ptr():
+        raise ValueError("anchor_reduce_bwd: out must not alias emb")
+    _dev(emb, dT, out)  # after the shape / dtype checks: those need no device
+    _launch("text_bwd", "anchor_reduce_bwd", 0.0, 16.0 * emb.numel(), "aaclip_anchor_reduce_bwd", _ptr(emb), n, dim,
+            _ptr(dT), col, dT.shape[1], _ptr(out), _stream())
+    return out
+
+
+def linear_wgrad_workspace(M: int, N: int, K: int, device) -> torch.Tensor:
+    nbytes = ctypes.c_size_t(0)
+    call("aaclip_linear_wgrad_workspace", M, N, K, ctypes.byref(nbytes))
+    return torch.empty(int(nbytes.value) // 4, device=device, dtype=torch.float32)
+
+
+def linear_wgrad(dy, x, *, out=None, workspace=None):
+    """dW [N, K] = dy[M, N]^T x[M, K], the weight gradient of a bias-free Linear (N, K % 64 == 0)."""
+    _rowmajor(dy, "dy")
+    _rowmajor(x, "x")
+    if dy.dtype != torch.float32 or x.dtype != torch.float32:
+        raise ValueError("linear_wgrad takes fp32 operands")
+    M, N = dy.shape
+    K = x.shape[1]
+    if x.shape[0] != M or M < 1 or N % 64 or K % 64 or N < 64 or K < 64:
+        raise ValueError(f"linear_wgrad: dy [M, N] and x [M, K] with M >= 1, N and K multiples of 64; got "
+                         f"{tuple(dy.shape)} {tuple(x.shape)}")
+    if out is None:
+        out = torch.empty(N, K, device=dy.device, dtype=torch.float32)
+    _rowmajor(out, "out")
+    if out.dtype != torch.float32 or tuple(out.shape) != (N, K):
+        raise ValueError("linear_wgrad: out must be fp32 [N, K]")
+    if workspace is None:
+        workspace = linear_wgrad_workspace(M, N, K, dy.device)
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous():
+        raise ValueError("linear_wgrad workspace must be contiguous fp32")
+    _dev(dy, x, out, workspace)  # after the shape / dtype checks: those need no device
+    _launch("text_bwd", "linear_wgrad", 2.0 * M * N * K, (M * (N + K) + 2 * N * K) * 4, "aaclip_linear_wgrad",
+            _ptr(dy), dy.stride(0), _ptr(x), x.stride(0), M, N, K, _ptr(workspace), workspace.numel() * 4, _ptr(out),
+            out.stride(0), _stream())
+    return out
+
+
+class _AnchorColumn(torch.autograd.Function):
+    """One anchor column normalize(mean_s normalize(emb[s])) with a backward to emb."""
+
+    @staticmethod
+    def forward(ctx, emb_in, emb):
+        T = torch.empty(emb.shape[1], 1, device=emb.device, dtype=torch.float32)
+        anchor_reduce(emb, T, 0)
+        ctx.save_for_backward(emb)
+        ctx.meta = (emb_in.shape, emb_in.dtype, emb_in.device)
+        return T[:, 0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dt):
+        (emb,) = ctx.saved_tensors
+        with torch.cuda.device(emb.device):
+            dT = dt.to(emb.device, torch.float32).reshape(-1, 1).contiguous()
+            demb = anchor_reduce_bwd(emb, dT, 0)
+        return demb.reshape(ctx.meta[0]).to(device=ctx.meta[2], dtype=ctx.meta[1]), None
+
+
+def anchor_column(emb: torch.Tensor) -> torch.Tensor:
+    """[dim] = normalize(mean_s normalize(emb[s])) (aaclip_anchor_reduce, the bits anchor_reduce
+    writes into a T column). When emb carries grad the result does too (aaclip_anchor_reduce_bwd)."""
+    _dev(emb)
+    e = emb.detach().to(torch.float32).contiguous()
+    if torch.is_grad_enabled() and emb.requires_grad:
+        with torch.cuda.device(e.device):
+            return _AnchorColumn.apply(emb, e)
+    T = torch.empty(e.shape[1], 1, device=e.device, dtype=torch.float32)
+    anchor_reduce(e, T, 0)
+    return T[:, 0]
+
+
 def anomaly_map(levels, T, out, grid_ws, *, g, ksize, sigma, normalize=True):
     """Test-branch map of all levels: patch_scores into grid_ws (>= B*g*g fp32), then blur_upsample."""
     _dev(*levels, T, out, grid_ws)

@@ -114,6 +114,20 @@ __device__ __forceinline__ void softmax_channels(float (&v)[C][N], int p) {
   for (int c = 0; c < C; ++c) v[c][p] *= inv;
 }
 
+// ---------------------------------------------------------------- fp32 activations
+// The exact forms the fp32 GEMM epilogue applies (gemm.hip epilogue_store1). Shared with the
+// elementwise aaclip_act (text_bwd.hip), which the training forward runs on a stored c_fc
+// pre-activation: the same function on the same value, so the training forward's bits are
+// the eval path's.
+__device__ __forceinline__ float gelu_erf(float v) {
+  return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+}
+// QuickGELU (reference transformer.py:46-49: x * sigmoid(1.702 x)). Exact form for the
+// fp32 parity kernel: the same expf/division as torch.sigmoid's fp32 CPU path.
+__device__ __forceinline__ float qgelu_exact(float v) { return v * (1.0f / (1.0f + expf(-1.702f * v))); }
+// nn.LeakyReLU(0.01), written as the epilogue writes it
+__device__ __forceinline__ float leaky_relu(float v) { return v >= 0.f ? v : 0.01f * v; }
+
 // ---------------------------------------------------------------- launch checking
 #define AACLIP_CHECK_LAUNCH()                                 \
   do {                                                        \

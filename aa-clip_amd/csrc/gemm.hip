@@ -121,10 +121,6 @@ __device__ __forceinline__ int remap_row(const GemmArgs& a, int m) {
   return a.row_group > 0 ? (m / a.row_group) * a.row_group_out + a.row_offset + (m % a.row_group) : m;
 }
 
-__device__ __forceinline__ float gelu_erf(float v) {
-  return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
-}
-
 // GELU for the bf16-input kernel: v * sigmoid(v * P(v^2)), P quadratic, fitted
 // (minimax on [-12, 12]) to the erf form: |error| <= 2.6e-5 absolute, an order
 // below the bf16 rounding of the output for |y| >= 0.01. The clamp keeps the
@@ -132,7 +128,7 @@ __device__ __forceinline__ float gelu_erf(float v) {
 // v_exp + one v_rcp per element, vs 16 + 2 for an erfc-polynomial form; the c_fc
 // epilogue is VALU-bound (all waves of the chip run it at once, no MFMA to hide
 // behind). -log2(e) is folded into the coefficients so v_exp_f32 (2^x) applies
-// directly. The fp32 parity kernel keeps the exact erff form (gelu_erf).
+// directly. The fp32 parity kernel keeps the exact erff form (gelu_erf, common.h).
 __device__ __forceinline__ float gelu_fast(float v) {
   const float vc = __builtin_amdgcn_fmed3f(v, -8.0f, 8.0f);
   const float s = vc * vc;
@@ -153,10 +149,6 @@ __device__ __forceinline__ float2_t gelu_fast2(float2_t v) {
   const float2_t d = float2_t{__builtin_amdgcn_exp2f(w[0]), __builtin_amdgcn_exp2f(w[1])} + one;
   return v * float2_t{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
 }
-
-// QuickGELU (reference transformer.py:46-49: x * sigmoid(1.702 x)). Exact form for the
-// fp32 parity kernel: the same expf/division as torch.sigmoid's fp32 CPU path.
-__device__ __forceinline__ float qgelu_exact(float v) { return v * (1.0f / (1.0f + expf(-1.702f * v))); }
 
 // 16-bit kernels, a column pair in packed f32: v * rcp(1 + 2^(-1.702 log2(e) v)); the
 // argument is clamped to |.| <= 64 (exp2 stays finite, sigmoid is 0/1 to 1e-19 there).

@@ -13,9 +13,11 @@
   calculate_seg_loss         forward_utils.py:219-227 — FocalLoss() + the two
       BinaryDiceLoss() terms in aaclip_seg_loss, backward in aaclip_seg_loss_bwd.
       With the map above this is train.py:86-100 from the anchors / features down
-      to loss.backward(). The text and image towers have no backward: encode_text
-      and get_adapted_*_text_embedding return tensors without a grad_fn, so the
-      anchors (or features) are the leaves.
+      to loss.backward(). With grad enabled and a trainable text_adapter,
+      get_adapted_single_class_text_embedding's anchors carry a grad_fn through
+      aaclip_anchor_reduce_bwd and the text tower's backward (TextEngine.encode_train)
+      into the four text_adapter weights: train.py:62-72, :87-100 runs as written.
+      The image towers have no backward (stage 2).
   anomaly_map_multilevel     the fused form of test.py:86-93 (all levels in one
       stream kernel, level sum before blur+upsample).
   metrics_eval               forward_utils.py:233-280 — on device (aaclip_metrics_eval:
@@ -58,11 +60,20 @@ def get_adapted_single_class_text_embedding(model, dataset_name, class_name, dev
         real_name = REAL_NAMES[dataset_name][class_name]
     device = torch.device(device)
     T = None
+    cols = []
     for col, sentences in enumerate(_sentences(real_name)):
-        emb = model.encode_text(tokenize(sentences).to(device)).to(torch.float32).contiguous()
+        emb = model.encode_text(tokenize(sentences).to(device))
+        if torch.is_grad_enabled() and emb.requires_grad:
+            # stage 1 (train.py:62-72): the same anchor kernel per column, with a backward to
+            # the embeddings (aaclip_anchor_reduce_bwd) and on into the text adapter
+            cols.append(ops.anchor_column(emb))
+            continue
+        emb = emb.to(torch.float32).contiguous()
         if T is None:
             T = torch.empty(emb.shape[1], 2, device=emb.device, dtype=torch.float32)
         ops.anchor_reduce(emb, T, col)
+    if cols:
+        T = torch.stack(cols, dim=1)
     return T.to(device)
 
 

@@ -5,7 +5,8 @@ ModuleDict{layer_adapters, seg_proj, det_proj}, `text_adapter` ModuleList,
 `t_w`, `i_w`, `levels`, ...) and state-dict keys. `forward` / `encode_text`
 run on the MI355X engines (aaclip.engine) built from the module's current
 parameters; the packed device copies are rebuilt whenever a parameter changes
-(load_state_dict, in-place edits: tracked by tensor version counters).
+(load_state_dict, in-place edits: tracked by tensor version counters). `encode_text`
+under grad mode with a trainable `text_adapter` is differentiable into it (stage 1).
 
 Compute dtype of the visual tower: fp16 MFMA by default — the mode that meets the
 north_star map contract (1e-3 abs + 1e-2 rel, argmax labels beyond rounding ties)
@@ -119,4 +120,11 @@ class AdaptedCLIP(nn.Module):
         if not adapt_text:
             return self.clipmodel.encode_text(text)
         eng = self.clipmodel.text_engine(self.text_adapter.state_dict(), self.text_adapt_until, self.t_w)
+        # stage 1 (reference train.py:38-114): with grad enabled and a trainable text adapter the
+        # result has a grad_fn into the adapter weights, read live (TextEngine.encode_train: the
+        # same launches and bits, activations kept for the HIP backward). Every other call is
+        # the forward-only path.
+        weights = [m.fc[0].weight for m in self.text_adapter]
+        if torch.is_grad_enabled() and any(w.requires_grad for w in weights):
+            return eng.encode_train(text, weights)
         return eng.encode(text)

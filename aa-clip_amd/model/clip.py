@@ -177,6 +177,7 @@ class CLIP(nn.Module):
         self._init_text()
         self._text_engine = None
         self._text_sig = None
+        self._text_asig = None
 
     def _init_text(self):
         # reference TextTransformer.init_parameters (transformer.py:597-617)
@@ -196,13 +197,19 @@ class CLIP(nn.Module):
     def text_engine(self, adapter_sd=None, adapt_until=3, adapt_weight=0.1):
         from aaclip.engine import TextEngine
         from .adapter import param_signature
-        sig = (param_signature(self, prefix_excl="visual."), None if adapter_sd is None else
-               tuple((k, v.data_ptr(), v._version) for k, v in adapter_sd.items()), adapt_until, adapt_weight)
+        # the frozen tower and the adapter are tracked apart: a changed adapter tensor (every
+        # optimizer.step() of stage 1) rebinds the adapter weights only; the ~150 MB frozen
+        # packing (and its transposes for the backward) is rebuilt only when the tower changes
+        sig = (param_signature(self, prefix_excl="visual."), adapter_sd is None, adapt_until, adapt_weight)
+        asig = None if adapter_sd is None else tuple((k, v.data_ptr(), v._version) for k, v in adapter_sd.items())
         if self._text_engine is None or self._text_sig != sig:
             self._text_engine = TextEngine(self.text_params(), adapter_sd, text_adapt_until=adapt_until,
                                            text_adapt_weight=adapt_weight, dtype=torch.float32,
                                            quick_gelu=self.transformer.quick_gelu)
-            self._text_sig = sig
+            self._text_sig, self._text_asig = sig, asig
+        elif self._text_asig != asig:
+            self._text_engine.set_adapter(adapter_sd)
+            self._text_asig = asig
         return self._text_engine
 
     def encode_text(self, text, normalize: bool = False):

@@ -459,6 +459,106 @@ int aaclip_patch_logits_bwd(int in_dtype, const void* f, int64_t ld, const float
                             float* workspace, size_t workspace_bytes, float* dT, float* df, void* stream);
 
 /*
+ * ---- Backward of the adapted text tower (stage 1: train.py:38-114 trains text_adapter) ----
+ * Added under ABI version 8 as the loss head was: additions only; the loader refuses a
+ * library that lacks one. All fp32, deterministic (no floating-point atomics, fixed reduction
+ * orders: two launches give the same bits); a row's / sequence's result depends on that row
+ * / sequence alone; every argument is checked before the first launch; nothing allocates,
+ * synchronises or reads on the host. The input-gradient GEMMs dX = dY . W between them are
+ * aaclip_gemm on transposed weight copies. Only the four text_adapter weights get a
+ * gradient: no dW / db of the frozen tower, no bias or LayerNorm-parameter gradients.
+ */
+
+/*
+ * Backward of aaclip_attention (fp32): dqkv [batch*seq, 3*heads*64] (packed [dq|dk|dv], every
+ * element written) from the packed qkv the forward consumed and dout [batch*seq, heads*64].
+ * P = softmax(q k^T / 8) is recomputed from q, k (the forward's output is not needed: the
+ * softmax term is D_i = sum_j P_ij dP_ij), dP = dout v^T, dS = P (dP - D), dq = dS k / 8,
+ * dk = dS^T q / 8, dv = P^T dout. flags: AACLIP_ATTN_CAUSAL or 0. head_dim == 64, 1 <= seq <=
+ * 77 (the text context; one (sequence, head) per workgroup, its tiles in LDS), else
+ * AACLIP_ERR_ARG before any launch. dk / dv rows are summed over the queries in index order by
+ * that workgroup alone. dqkv must not alias qkv.
+ * Replaces: the autograd of F.multi_head_attention_forward's core (model/transformer.py:200,
+ * attn_mask of transformer.py:629-635) under model/adapter.py:125-128, train.py:99.
+ */
+int aaclip_attention_bwd(const float* qkv, const float* dout, float* dqkv, int batch, int seq, int heads,
+                         int head_dim, int flags, void* stream);
+
+/*
+ * dx = [residual +] d LN(x; w) / dx . dy per row: mean and rstd are recomputed from x (eps 1e-5,
+ * biased variance, aaclip_layernorm's arithmetic), g = dy w, xh = (x - mean) rstd,
+ * dx = rstd (g - mean(g) - xh mean(g xh)). No dw / db. residual (optional, NULL = none) is the
+ * incoming residual-stream gradient and may be dx itself (with the same leading dimension), as
+ * may dy. width 768 or 1024 (what aaclip_layernorm takes); ld* >= width, multiples of 4.
+ * Replaces: the autograd of ln_1 / ln_2 (model/transformer.py:37-43, :254-257) under train.py:99.
+ */
+int aaclip_layernorm_bwd(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* w,
+                         const float* residual, int64_t ldr, float* dx, int64_t lddx, int rows, int width,
+                         void* stream);
+
+/*
+ * Backward of aaclip_eot_ln: g [n_seq*ctx, width] (every row written) = the ln_final backward
+ * of dy[s] at row s*ctx + argmax_t tokens[s,t] (first occurrence, as the forward), zero in
+ * every other row. x is the [n_seq*ctx, width] residual stream the forward read.
+ * Replaces: the autograd of model/adapter.py:138-140 under train.py:99.
+ */
+int aaclip_eot_ln_bwd(const float* dy, const float* x, const int32_t* tokens, const float* w, float* g,
+                      int n_seq, int ctx, int width, void* stream);
+
+/*
+ * y = f(x) elementwise, f selected by the GEMM epilogue flag `mode` (AACLIP_EPI_GELU,
+ * AACLIP_EPI_QGELU or AACLIP_EPI_LEAKY): the very device function the fp32 aaclip_gemm epilogue
+ * applies, so aaclip_gemm(BIAS) followed by aaclip_act gives the bits of aaclip_gemm(BIAS | f).
+ * The training forward stores the c_fc pre-activation this way (model/transformer.py:211-219).
+ * y may be x.
+ */
+int aaclip_act(int mode, const float* x, float* y, int64_t n, void* stream);
+
+/*
+ * dx = dy * f'(.) elementwise (dx may be dy). GELU (exact erf, nn.GELU) and QuickGELU
+ * (transformer.py:46-49) take ref = the PRE-activation: gelu'(v) = Phi(v) + v phi(v),
+ * quick'(v) = s + 1.702 v s (1 - s) with s = sigmoid(1.702 v). LeakyReLU(0.01)
+ * (model/adapter_modules.py:6-26) takes ref = the OUTPUT, whose sign is the input's: slope 1
+ * above 0, 0.01 at and below 0 (as torch's leaky_relu backward).
+ * Replaces: the autograd of those activations under train.py:99.
+ */
+int aaclip_act_bwd(int mode, const float* dy, const float* ref, float* dx, int64_t n, void* stream);
+
+/*
+ * Backward of aaclip_block_tail's adapter blend y = w u |x| / |u| + (1 - w) x
+ * (model/adapter.py:130-136; the norms are differentiated, as autograd does): with a = dy . u,
+ *   dx = (1 - w) dy + w (a / |u|) x / |x|        du = w (|x| / |u|) (dy - u a / |u|^2)
+ * one pass per row, norms summed in the forward's order. x is the PRE-blend block output, u the
+ * adapter output; dx is the gradient through x alone (the caller adds the adapter path du -> x).
+ * dx may be dy. width 768 or 1024.
+ */
+int aaclip_adapter_blend_bwd(const float* dy, const float* x, const float* u, float adapt_weight, float* dx,
+                             float* du, int rows, int width, void* stream);
+
+/*
+ * Backward of aaclip_anchor_reduce: demb [n, dim] from dT[:, col] (dT [dim, ncols] fp32)
+ * through T[:, col] = normalize(mean_s normalize(emb[s])). n <= 256, dim <= 1024 (the
+ * forward's limits). Replaces: the autograd of forward_utils.py:155-159 under train.py:99.
+ */
+int aaclip_anchor_reduce_bwd(const float* emb, int n, int dim, const float* dT, int col, int ncols,
+                             float* demb, void* stream);
+
+/*
+ * Weight gradient of a bias-free Linear y = x W^T: dW[n, k] = sum_m dY[m, n] X[m, k]
+ * (dY [M, N], X [M, K], dW [N, K]; leading dimensions in elements). Any M >= 1; N and K
+ * multiples of 64. Rows are cut into chunks of AACLIP_WGRAD_ROWS (a function of M alone); each
+ * chunk's partial [N, K] is accumulated over its rows in index order (fp32 FMA) into
+ * workspace, and a finalize pass sums the chunks in index order in fp64. workspace:
+ * aaclip_linear_wgrad_workspace bytes (ceil(M / AACLIP_WGRAD_ROWS) * N * K floats).
+ * Replaces: the autograd of the SimpleAdapter / SimpleProj Linear (model/adapter_modules.py:6-47)
+ * under train.py:99; the image adapters of stage 2 (1024 x 1024) take the same entry.
+ */
+#define AACLIP_WGRAD_ROWS 64
+int aaclip_linear_wgrad_workspace(int M, int N, int K, size_t* bytes);
+int aaclip_linear_wgrad(const float* dY, int64_t lddy, const float* X, int64_t ldx, int M, int N, int K,
+                        float* workspace, size_t workspace_bytes, float* dW, int64_t lddw, void* stream);
+
+/*
  * Full test-branch anomaly map for one batch: patch_scores (mode 0) into the
  * caller's workspace grid_ws (>= batch*g*g fp32), then blur + upsample into
  * out [batch, S, S]. Replaces: test.py:86-93 + forward_utils.py:196-213.
