@@ -5,7 +5,8 @@ the anomaly map / image score of test.py:80-93; TextEngine =
 AdaptedCLIP.encode_text / CLIP.encode_text (adapter.py:114-145,
 model/model.py:190-201) + the prompt-ensemble anchors (forward_utils.py:138-162), and
 TextEngine.encode_train, the same forward with a HIP backward into the text adapter
-weights (stage 1, train.py:38-114).
+weights (stage 1, train.py:38-114); VisualEngine.forward_train, forward() with a HIP
+backward into the image adapter weights (stage 2, train.py:117-174).
 
 Data layout in HBM (token-major "NLD", one row per token):
   x      fp32 [B*(P+1), 1024]   residual stream (kept fp32 across all 24 blocks)
@@ -153,17 +154,11 @@ class VisualEngine:
             for blk in self.blocks:
                 for k in (("w_fc", "w_pr") if self.fp8_mlp_only else ("w_qkv", "w_o", "w_fc", "w_pr")):
                     blk[k] = _quant_weight_fp8(blk[k])
-        self.w_adapt = [cdt(adapter[f"layer_adapters.{i}.fc.0.weight"]) for i in range(self.adapt_until)]
-        self.w_seg, relus = [], []
-        for i in range(len(self.levels)):
-            wt, r = _proj_weight(adapter, f"seg_proj.{i}")
-            self.w_seg.append(wt)
-            relus.append(r)
-        w_det, r_det = _proj_weight(adapter, "det_proj")
-        if len(set(relus + [r_det])) != 1:
-            raise ValueError("seg_proj/det_proj relu variants must agree")
-        self.relu = r_det
-        self.w_seg = [cdt(t) for t in self.w_seg[:-1]] + [cdt(torch.cat([self.w_seg[-1], w_det], 0))]
+        self._bwd = None  # transposed frozen block weights for the input-gradient GEMMs (forward_train)
+        # tests / debugging: blocks whose output gradient [R, 1024] each backward appends to
+        # tap_records as {"B", "n_tok", "taps": {block: tensor}} (empty: nothing is kept)
+        self.tap_blocks, self.tap_records = (), []
+        self.set_adapter(adapter)
         self._ws = {}
         self.poison = False  # tests: fill new workspaces with NaN (read-before-write screen)
         # predict(): projections straight into map partials (aaclip_gemm_scores +
@@ -175,6 +170,213 @@ class VisualEngine:
         # (aaclip_gemm_ksplit): the same split at every batch size, so per-image bits stay
         # independent of the batch composition. 0 / 1 = unsplit.
         self.cproj_ksplit = CPROJ_KSPLIT if (self.dtype != torch.float32 and not self.fp8) else 0
+
+    def set_adapter(self, adapter: dict):
+        """(Re)bind the image_adapter weights forward() / predict() read: adapt_until layer
+        adapters, one seg_proj per level and det_proj (packed behind the last level's rows, one
+        GEMM). The frozen packing (block weights, their transposes, the embeddings) is
+        untouched, so an optimizer step costs no repacking; fp32 device parameters are
+        referenced, not copied. Captured predict graphs hold the previous weights and are
+        dropped."""
+        cdt = lambda t: t.detach().to(self.device, self.dtype).contiguous()  # noqa: E731
+        self.w_adapt = [cdt(adapter[f"layer_adapters.{i}.fc.0.weight"]) for i in range(self.adapt_until)]
+        w_seg, relus = [], []
+        for i in range(len(self.levels)):
+            wt, r = _proj_weight(adapter, f"seg_proj.{i}")
+            w_seg.append(wt)
+            relus.append(r)
+        w_det, r_det = _proj_weight(adapter, "det_proj")
+        if len(set(relus + [r_det])) != 1:
+            raise ValueError("seg_proj/det_proj relu variants must agree")
+        self.relu = r_det
+        self.w_seg = [cdt(t) for t in w_seg[:-1]] + [cdt(torch.cat([w_seg[-1], w_det], 0))]
+        self._graph_cache, self._last_key = {}, None
+
+    # ------------------------------------------------------------------ training (stage 2)
+    def _bwd_weights(self):
+        """W^T copies of the frozen block weights: dX = dY . W is aaclip_gemm (C = A . W'^T)
+        with W' = W^T. Packed once per engine, on the first training call; block 0 never
+        needs a backward (no trainable weight lies below the adapter that follows it)."""
+        if self._bwd is None:
+            tr = lambda w: w.t().contiguous()  # noqa: E731
+            self._bwd = [None] + [dict(w_qkv=tr(b["w_qkv"]), w_o=tr(b["w_o"]), w_fc=tr(b["w_fc"]), w_pr=tr(b["w_pr"]))
+                                  for b in self.blocks[1:self.levels[-1]]]
+        return self._bwd
+
+    def forward_train(self, x: torch.Tensor, adapter_weights):
+        """forward() with a grad_fn into the image adapter (stage 2, reference train.py:117-174).
+        adapter_weights: the adapt_until layer-adapter weights [1024, 1024], one seg_proj weight
+        per level and the det_proj weight [768, 1024] (contiguous fp32 tensors on this engine's
+        device, normally the live nn.Parameters), read as they are at the call. The outputs are
+        bit-identical to forward()'s on the same weights; backward fills .grad of the weights
+        that require it, walks the tower down to the lowest layer adapter that does and computes
+        nothing for the frozen weights. fp32 engines and a single chunk only."""
+        if self.dtype != torch.float32 or self.fp8:
+            raise RuntimeError("the visual tower trains in fp32 only")
+        ws = list(adapter_weights)
+        L = len(self.levels)
+        if len(ws) != self.adapt_until + L + 1:
+            raise ValueError(f"expected {self.adapt_until + L + 1} adapter weights, got {len(ws)}")
+        for i, w in enumerate(ws):
+            want = (WIDTH, WIDTH) if i < self.adapt_until else (EMBED, WIDTH)
+            if w.device != self.device or w.dtype != torch.float32 or tuple(w.shape) != want or not w.is_contiguous():
+                raise ValueError(f"adapter weight {i} must be a contiguous fp32 {list(want)} tensor on {self.device}")
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[2] % PATCH:
+            raise ValueError("input must be [B, 3, S, S] with S a multiple of 14")
+        if x.shape[0] > self.max_chunk(x.shape[-1]):
+            raise ValueError(f"forward_train takes one chunk: at most {self.max_chunk(x.shape[-1])} images of "
+                             f"{x.shape[-1]} px, got {x.shape[0]}")
+        out = _VisualTrain.apply(self, x, *ws)
+        return list(out[:L]), out[L]
+
+    @_on_device
+    def _train_forward(self, x, ws, lowest):
+        """The launches of forward_raw() + forward() in fp32, with c_fc's pre-activation kept
+        (aaclip_gemm bias-only + aaclip_act: the epilogue's own device function) and every
+        block above `lowest` writing fresh buffers. lowest = index of the lowest layer adapter
+        that needs a gradient (None: only seg_proj / det_proj train, nothing of the tower is
+        kept beyond the level taps)."""
+        x = x.detach().to(self.device, torch.float32).contiguous()
+        B, _, S, _ = x.shape
+        g = S // PATCH
+        P = g * g
+        n_tok = P + 1
+        if self.pos.shape[0] != n_tok:
+            raise ValueError(f"positional embedding has {self.pos.shape[0]} rows, image needs {n_tok} "
+                             "(resize it at load time, reference model/model.py:395-426)")
+        R, W, dev = B * n_tok, WIDTH, self.device
+        e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
+        cols, X, H = e(B * P, KPATCH), e(R, W), e(R, W)
+        ops.im2col(x, cols, PATCH)
+        ops.gemm(cols, self.conv, X, row_group=P, row_group_out=n_tok, row_offset=1)
+        ops.embed_ln(X, self.cls, self.pos, self.ln_pre, self.blocks[0]["ln1"], H, B, n_tok)
+        lvl = {lv: j for j, lv in enumerate(self.levels)}
+        last, L, au = self.levels[-1], len(self.levels), self.adapt_until
+        qkv, att, fc, u = e(R, 3 * W), e(R, W), e(R, 4 * W), e(R, W)
+        fc_pre = fc
+        taps = [e(B * P, W) for _ in range(L)]
+        saved, x_tap = {}, {}
+        for i in range(last):
+            blk = self.blocks[i]
+            keep = lowest is not None and i > lowest        # this block has a backward
+            adapt = i < au
+            keep_blend = lowest is not None and adapt and i >= lowest
+            if keep:
+                qkv, att, fc_pre = e(R, 3 * W), e(R, W), e(R, 4 * W)
+            ops.gemm(H, blk["w_qkv"], qkv, bias=blk["b_qkv"])
+            ops.attention(qkv, att, B, n_tok, HEADS)
+            x_in = X
+            x_mid = e(R, W) if keep else X
+            ops.gemm(att, blk["w_o"], x_mid, bias=blk["b_o"], residual=x_in)
+            ops.layernorm(x_mid, blk["ln2"][0], blk["ln2"][1], H)
+            if keep:
+                ops.gemm(H, blk["w_fc"], fc_pre, bias=blk["b_fc"])
+                ops.act(fc_pre, self.act, out=fc)
+            else:
+                ops.gemm(H, blk["w_fc"], fc, bias=blk["b_fc"], gelu=self.act)
+            X = e(R, W) if (keep or keep_blend) else x_mid
+            ops.gemm(fc, blk["w_pr"], X, bias=blk["b_pr"], residual=x_mid)
+            if keep:
+                saved[i] = dict(x_in=x_in, qkv=qkv, att=att, x_mid=x_mid, fc_pre=fc_pre)
+            tap = taps[lvl[i + 1]] if (i + 1) in lvl else None
+            nxt = self.blocks[i + 1]["ln1"] if i + 1 < last else None
+            uu = None
+            if adapt:
+                if keep_blend:
+                    u = e(R, W)
+                ops.gemm(X, ws[i], u, leaky=True)
+                if keep_blend:  # the blend is in place: keep the pre-blend x, blend a copy
+                    saved.setdefault(i, {}).update(x_pre=X, u=u)
+                    X = X.clone()
+                uu = u
+            if uu is not None or nxt is not None or tap is not None:
+                ops.block_tail(X, n_tok, u=uu, adapt_weight=self.i_w, ln=nxt, h=H if nxt else None,
+                               post=self.ln_post, tap=tap)
+            if tap is not None and lowest is not None and i >= lowest:
+                x_tap[lvl[i + 1]] = X  # the stream the tap read: the blocks above write fresh buffers
+        # projections: the level GEMMs of forward_raw (det_proj packed behind the last level)
+        seg_raw = []
+        for j in range(L - 1):
+            seg_raw.append(ops.gemm(taps[j], ws[au + j], e(B * P, EMBED), leaky=self.relu))
+        tail = ops.gemm(taps[L - 1], torch.cat([ws[au + L - 1], ws[au + L]], 0), e(B * P, 2 * EMBED), leaky=self.relu)
+        seg_raw.append(tail[:, :EMBED])
+        det_raw = tail[:, EMBED:]
+        out = [ops.l2_normalize(s_, e(B * P, EMBED)).view(B, P, EMBED) for s_ in seg_raw]
+        det = e(B, EMBED)
+        ops.image_score(det_raw, B, P, e(B * ((P + 15) // 16) * EMBED), det=det)
+        st = dict(B=B, P=P, n_tok=n_tok, lowest=lowest, blocks=saved, x_tap=x_tap, taps=taps, seg_raw=seg_raw,
+                  det_raw=det_raw)
+        return out, det, st
+
+    @_on_device
+    def _train_backward(self, st, ws, need, dseg, ddet):
+        """Gradients of the adapter weights `need` marks, from dseg (one [B, P, 768] per level)
+        and ddet [B, 768]."""
+        B, P, n_tok, lowest = st["B"], st["P"], st["n_tok"], st["lowest"]
+        R, W, dev = B * n_tok, WIDTH, self.device
+        L, au, last = len(self.levels), self.adapt_until, self.levels[-1]
+        e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
+        wt = lambda w: w.detach().t().contiguous()  # noqa: E731
+        grads = [None] * len(ws)
+        # a level's tap feeds the tower backward only if a trainable adapter lies at or below it
+        flows = [lowest is not None and lv - 1 >= lowest for lv in self.levels]
+        dtaps = [None] * L
+        for j in range(L + 1):  # the L seg projections, then det (on the last level's tap)
+            lv = min(j, L - 1)
+            if not (need[au + j] or flows[lv]):
+                continue
+            if j < L:  # seg_j = normalize(act(tap_j W^T)) per patch row
+                raw = st["seg_raw"][j]
+                d = ops.l2_normalize_bwd(dseg[j].reshape(B * P, EMBED).contiguous(), raw)
+            else:      # det = mean_p normalize(act(tap_last W^T))
+                raw = st["det_raw"]
+                d = ops.l2_normalize_bwd(ddet, raw, group=P, scale=1.0 / P)
+            if self.relu:
+                ops.act_bwd(d, raw.contiguous(), "leaky", out=d)
+            if need[au + j]:
+                grads[au + j] = ops.linear_wgrad(d, st["taps"][lv])
+            if flows[lv]:
+                if dtaps[lv] is None:
+                    dtaps[lv] = ops.gemm(d, wt(ws[au + j]), e(B * P, W))
+                else:
+                    ops.gemm(d, wt(ws[au + j]), dtaps[lv], residual=dtaps[lv])
+        if lowest is None:
+            return grads
+        bw = self._bwd_weights()
+        lvl = {lv: j for j, lv in enumerate(self.levels)}
+        g = torch.zeros(R, W, device=dev, dtype=torch.float32)
+        d_qkv, d_wide, d_w, du = e(R, 3 * W), e(R, 4 * W), e(R, W), e(R, W)
+        attn_ws = ops.attention_bwd_tiled_workspace(B, n_tok, HEADS, dev)
+        act_mode = "quick" if self.act == "quick" else "gelu"
+        taps = {}
+        for i in range(last - 1, lowest - 1, -1):
+            j = lvl.get(i + 1)
+            if j is not None and dtaps[j] is not None:  # the level tap read x after block i (blend included)
+                ops.tap_ln_bwd(dtaps[j], st["x_tap"][j], self.ln_post[0], g, B, n_tok)
+            sv = st["blocks"].get(i, {})
+            if "u" in sv:  # x <- w u |x| / |u| + (1 - w) x after block i, u = LeakyReLU(x Wa_i^T)
+                ops.adapter_blend_bwd(g, sv["x_pre"], sv["u"], self.i_w, dx=g, du=du)
+                ops.act_bwd(du, sv["u"], "leaky", out=du)
+                if need[i]:
+                    grads[i] = ops.linear_wgrad(du, sv["x_pre"])
+                if i > lowest:
+                    ops.gemm(du, wt(ws[i]), g, residual=g)
+            if i in self.tap_blocks:  # diagnostic: dL/d(block i's own output), the adapter path included
+                taps[i] = g.clone() if i > lowest else ops.gemm(du, wt(ws[i]), e(R, W), residual=g)
+            if i == lowest:
+                break
+            blk, bt = self.blocks[i], bw[i]
+            ops.gemm(g, bt["w_pr"], d_wide)                                    # 1. d_act = g . W_pr
+            ops.act_bwd(d_wide, sv["fc_pre"], act_mode, out=d_wide)            # 2. d_pre = d_act gelu'(fc_pre)
+            ops.gemm(d_wide, bt["w_fc"], d_w)                                  # 3. d_h2 = d_pre . W_fc
+            ops.layernorm_bwd(d_w, sv["x_mid"], blk["ln2"][0], residual=g, out=g)  # 4. g_mid
+            ops.gemm(g, bt["w_o"], d_w)                                        # 5. d_att = g_mid . W_o
+            ops.attention_bwd_tiled(sv["qkv"], sv["att"], d_w, B, n_tok, HEADS, dqkv=d_qkv, workspace=attn_ws)  # 6.
+            ops.gemm(d_qkv, bt["w_qkv"], d_w)                                  # 7. d_h1 = d_qkv . W_qkv
+            ops.layernorm_bwd(d_w, sv["x_in"], blk["ln1"][0], residual=g, out=g)   # 8. g_in
+        if self.tap_blocks:
+            self.tap_records.append(dict(B=B, n_tok=n_tok, taps=taps))
+        return grads
 
     # ------------------------------------------------------------------ workspace
     def _workspace(self, B: int, S: int, slot: int = 0):
@@ -572,6 +774,30 @@ class VisualEngine:
         run.workspaces = held
         run.slot0 = slot0  # the private workspace slots (tools / bench diagnostics re-capture on them)
         return run
+
+
+class _VisualTrain(torch.autograd.Function):
+    """VisualEngine.forward with a backward into the image adapter weights (stage 2)."""
+
+    @staticmethod
+    def forward(ctx, engine, x, *ws):
+        need = ctx.needs_input_grad[2:]
+        low = [i for i in range(engine.adapt_until) if need[i]]
+        out, det, st = engine._train_forward(x, [w.detach() for w in ws], low[0] if low else None)
+        ctx.engine, ctx.st = engine, st
+        ctx.save_for_backward(*ws)
+        return (*out, det)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *douts):
+        ws = ctx.saved_tensors
+        need = list(ctx.needs_input_grad[2:])
+        eng = ctx.engine
+        d = [t.to(eng.device, torch.float32).contiguous() for t in douts]
+        grads = eng._train_backward(ctx.st, [w.detach() for w in ws], need, d[:-1], d[-1])
+        ctx.st = None
+        return (None, None, *grads)
 
 
 class TextEngine:

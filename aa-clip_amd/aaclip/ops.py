@@ -932,6 +932,90 @@ def linear_wgrad(dy, x, *, out=None, workspace=None):
     return out
 
 
+# ------------------------------------------------------------------------ stage-2 backward
+def attention_bwd_tiled_workspace(batch: int, seq: int, heads: int, device) -> torch.Tensor:
+    nbytes = ctypes.c_size_t(0)
+    call("aaclip_attention_bwd_tiled_workspace", batch, seq, heads, ctypes.byref(nbytes))
+    return torch.empty(int(nbytes.value) // 4, device=device, dtype=torch.float32)
+
+
+def attention_bwd_tiled(qkv, out, dout, batch: int, seq: int, heads: int, *, dqkv=None, workspace=None):
+    """dqkv [batch*seq, 3*heads*64] of the fp32 non-causal attention core, any seq >= 1, from
+    the packed qkv, the forward's output out and dout (both [batch*seq, heads*64])."""
+    hd = 64
+    if batch < 1 or heads < 1 or seq < 1:
+        raise ValueError("attention_bwd_tiled needs batch, heads and seq >= 1")
+    if batch * heads > 65535:
+        raise ValueError("attention_bwd_tiled: batch * heads must be <= 65535")
+    _f32c(qkv, "qkv", (batch * seq, 3 * heads * hd))
+    _f32c(out, "out", (batch * seq, heads * hd))
+    _f32c(dout, "dout", (batch * seq, heads * hd))
+    if dqkv is None:
+        dqkv = torch.empty_like(qkv)
+    _f32c(dqkv, "dqkv", qkv.shape)
+    if dqkv.data_ptr() in (qkv.data_ptr(), out.data_ptr(), dout.data_ptr()):
+        raise ValueError("attention_bwd_tiled: dqkv must not alias qkv, out or dout")
+    if workspace is None:
+        workspace = attention_bwd_tiled_workspace(batch, seq, heads, qkv.device)
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous():
+        raise ValueError("attention_bwd_tiled workspace must be contiguous fp32")
+    for t in (qkv, out, dout, dqkv, workspace):
+        if t.data_ptr() % 16:
+            raise ValueError("attention_bwd_tiled operands must be 16-byte aligned")
+    _dev(qkv, out, dout, dqkv, workspace)  # after the shape / dtype checks: those need no device
+    # 2 launches: S twice + dP + dQ, and S + dP + dV + dK: 16 seq^2 hd FLOPs per (image, head)
+    _launch("visual_bwd", "attention_bwd_tiled", 16.0 * batch * heads * seq * seq * hd,
+            (3 * qkv.numel() + 3 * dout.numel()) * 4, "aaclip_attention_bwd_tiled", _ptr(qkv), _ptr(out), _ptr(dout),
+            _ptr(dqkv), batch, seq, heads, hd, _ptr(workspace), workspace.numel() * 4, _stream())
+    return dqkv
+
+
+def tap_ln_bwd(dtap, x, w, g, batch: int, n_tok: int):
+    """g[b, t] += LN_bwd(dtap[b, t - 1]; x[b, t], w) for the token rows t >= 1 (in place; CLS rows
+    of g untouched): the backward of block_tail's level tap through ln_post."""
+    if x.dim() != 2 or x.shape[1] not in (768, 1024) or batch < 1 or n_tok < 2 or x.shape[0] != batch * n_tok:
+        raise ValueError("x must be [batch*n_tok, 768 | 1024] with n_tok >= 2")
+    width = x.shape[1]
+    _f32c(x, "x")
+    _f32c(g, "g", x.shape)
+    _f32c(dtap, "dtap", (batch * (n_tok - 1), width))
+    _f32c(w, "w", (width,))
+    if g.data_ptr() in (x.data_ptr(), dtap.data_ptr()):
+        raise ValueError("tap_ln_bwd: g must not alias x or dtap")
+    for t in (dtap, x, w, g):
+        if t.data_ptr() % 16:
+            raise ValueError("tap_ln_bwd operands must be 16-byte aligned")
+    _dev(dtap, x, w, g)  # after the shape / dtype checks: those need no device
+    _launch("visual_bwd", "tap_ln_bwd", 0.0, 16.0 * x.numel(), "aaclip_tap_ln_bwd", _ptr(dtap), _ptr(x), _ptr(w),
+            _ptr(g), batch, n_tok, width, _stream())
+    return g
+
+
+def l2_normalize_bwd(dy, x, *, group: int = 0, scale: float = 1.0, out=None):
+    """dx of y = x / max(|x|, 1e-12) per row of x [rows, 768 | 1024]. group == 0: dy is
+    [rows, width]; group > 0: row r takes scale * dy[r // group] (dy [rows / group, width]),
+    the backward of normalize(x).view(-1, group, width).mean(1) with scale = 1 / group."""
+    _f32rows(x, "x")
+    rows, width = x.shape
+    if width not in (768, 1024):
+        raise ValueError("l2_normalize_bwd supports widths 768 and 1024")
+    if group < 0 or (group > 0 and rows % group):
+        raise ValueError("l2_normalize_bwd: rows must be a multiple of group")
+    _f32rows(dy, "dy", (rows // group if group else rows, width))
+    if out is None:
+        out = torch.empty(rows, width, device=x.device, dtype=torch.float32)
+    _f32rows(out, "out", x.shape)
+    if out.data_ptr() == x.data_ptr():
+        raise ValueError("l2_normalize_bwd: out must not alias x")
+    if out.data_ptr() == dy.data_ptr() and (group or out.stride(0) != dy.stride(0)):
+        raise ValueError("l2_normalize_bwd: out may alias dy only row for row")
+    _dev(dy, x, out)  # after the shape / dtype checks: those need no device
+    _launch("visual_bwd", "l2_normalize_bwd", 0.0, 12.0 * rows * width, "aaclip_l2_normalize_bwd", _ptr(dy),
+            dy.stride(0), int(group), float(scale), _ptr(x), x.stride(0), _ptr(out), out.stride(0), rows, width,
+            _stream())
+    return out
+
+
 class _AnchorColumn(torch.autograd.Function):
     """One anchor column normalize(mean_s normalize(emb[s])) with a backward to emb."""
 

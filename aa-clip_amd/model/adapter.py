@@ -5,8 +5,10 @@ ModuleDict{layer_adapters, seg_proj, det_proj}, `text_adapter` ModuleList,
 `t_w`, `i_w`, `levels`, ...) and state-dict keys. `forward` / `encode_text`
 run on the MI355X engines (aaclip.engine) built from the module's current
 parameters; the packed device copies are rebuilt whenever a parameter changes
-(load_state_dict, in-place edits: tracked by tensor version counters). `encode_text`
-under grad mode with a trainable `text_adapter` is differentiable into it (stage 1).
+(load_state_dict, in-place edits: tracked by tensor version counters; a changed adapter is
+re-bound without repacking the frozen tower). `encode_text` under grad mode with a trainable
+`text_adapter` is differentiable into it (stage 1), and so is `forward` into a trainable
+`image_adapter` in the fp32 mode (stage 2).
 
 Compute dtype of the visual tower: fp16 MFMA by default — the mode that meets the
 north_star map contract (1e-3 abs + 1e-2 rel, argmax labels beyond rounding ties)
@@ -69,6 +71,7 @@ class AdaptedCLIP(nn.Module):
         self._init_weights_()
         self._vis = None
         self._vis_sig = None
+        self._vis_asig = None
 
     def _init_weights_(self):
         for p in self.image_adapter.parameters():
@@ -81,15 +84,22 @@ class AdaptedCLIP(nn.Module):
     # ------------------------------------------------------------------ engines
     def visual_engine(self):
         from aaclip.engine import VisualEngine
-        sig = (param_signature(self.image_encoder), param_signature(self.image_adapter), tuple(self.levels),
-               self.image_adapt_until, self.i_w, self.compute_dtype)
+        # the frozen tower's packing (~1.2 GB in fp32, plus its transposes once training has
+        # begun) is keyed on image_encoder alone; a changed image_adapter (load_state_dict, an
+        # optimizer step) only re-binds the adapter weights (VisualEngine.set_adapter)
+        sig = (param_signature(self.image_encoder), tuple(self.levels), self.image_adapt_until, self.i_w,
+               self.compute_dtype)
+        asig = param_signature(self.image_adapter)
         if self._vis is None or self._vis_sig != sig:
             vp = {"visual." + k: v for k, v in self.image_encoder.state_dict().items()}
             self._vis = VisualEngine(vp, self.image_adapter.state_dict(), levels=self.levels,
                                      image_adapt_until=self.image_adapt_until, image_adapt_weight=self.i_w,
                                      dtype=self.compute_dtype,
                                      quick_gelu=self.image_encoder.transformer.quick_gelu)
-            self._vis_sig = sig
+            self._vis_sig, self._vis_asig = sig, asig
+        elif self._vis_asig != asig:
+            self._vis.set_adapter(self.image_adapter.state_dict())
+            self._vis_asig = asig
         return self._vis
 
     # ------------------------------------------------------------------ API
@@ -104,9 +114,26 @@ class AdaptedCLIP(nn.Module):
         cls_features, _ = eng.encode(x, [], patch_features=True)
         return [eng.patch_features()], cls_features
 
+    def _adapter_weights(self):
+        ad = self.image_adapter
+        return ([m.fc[0].weight for m in ad["layer_adapters"]] + [m.weight for m in ad["seg_proj"]]
+                + [ad["det_proj"].weight])
+
     def forward(self, x):
-        """(list[len(levels)] of [B, P, 768] unit-norm patch features, det [B, 768])."""
-        return self.visual_engine().forward(x)
+        """(list[len(levels)] of [B, P, 768] unit-norm patch features, det [B, 768]).
+
+        Stage 2 (reference train.py:117-174): with grad mode on, compute_dtype float32 and at
+        least one image_adapter weight requiring grad, the same tensors come back with a grad_fn
+        into the image adapter weights, read live (VisualEngine.forward_train: the same launches
+        and bits, activations kept for the HIP backward; one chunk). Every other call -- no_grad,
+        a frozen image adapter, the 16-bit and fp8 modes even under grad -- is the forward-only
+        path, unchanged."""
+        eng = self.visual_engine()
+        if torch.is_grad_enabled() and self.compute_dtype == torch.float32:
+            weights = self._adapter_weights()
+            if any(w.requires_grad for w in weights):
+                return eng.forward_train(x, weights)
+        return eng.forward(x)
 
     def predict(self, x, text_features, domain="Industrial", streams=1):
         """Fused test path (test.py:80-93): (anomaly map [B,S,S], image score [B]), fp32.

@@ -558,6 +558,63 @@ int aaclip_linear_wgrad_workspace(int M, int N, int K, size_t* bytes);
 int aaclip_linear_wgrad(const float* dY, int64_t lddy, const float* X, int64_t ldx, int M, int N, int K,
                         float* workspace, size_t workspace_bytes, float* dW, int64_t lddw, void* stream);
 
+/* ------------------------------------------------------------------ stage-2 backward
+ * Backward of the adapted visual tower (visual_bwd.hip; train.py:117-174 trains image_adapter
+ * only). fp32, deterministic (no floating-point atomics, fixed reduction orders), image / row
+ * local; arguments are checked before the first launch, nothing allocates, synchronises or
+ * reads on the host. The rest of the stage-2 backward is aaclip_layernorm_bwd, aaclip_act /
+ * aaclip_act_bwd, aaclip_adapter_blend_bwd, aaclip_linear_wgrad and aaclip_gemm on transposed
+ * weight copies. Only the image_adapter weights get a gradient.
+ */
+
+/*
+ * Backward of the fp32, non-causal aaclip_attention for any sequence length (the visual tower:
+ * 577 tokens at 336 px, 1370 at 518 px; aaclip_attention_bwd holds a whole sequence in LDS and
+ * stops at 77). qkv [batch*seq, 3*heads*64] is the packed input the forward consumed, out
+ * [batch*seq, heads*64] the forward's output, dout its gradient; dqkv (packed [dq|dk|dv], every
+ * element written) must not alias an input. head_dim == 64, seq >= 1, batch*heads <= 65535.
+ * On v_mfma_f32_16x16x4_f32 with 64-row tiles in padded LDS, two launches:
+ *   query blocks (image, head, 64 queries): pass 1 over the key tiles gives the row
+ *     log-sum-exp, D_i = dout_i . out_i comes from the saved output (both stored in workspace,
+ *     [batch, heads, seq] each); pass 2 forms P = exp(S - lse), dP = dout v^T,
+ *     dS = P (dP - D), dq = dS k / 8;
+ *   key blocks (image, head, 64 keys): walk the query tiles in index order with the stored lse
+ *     and D: dv = P^T dout, dk = dS^T q / 8.
+ * Each output row is summed by one wave in a fixed order; keys / queries past the end of a
+ * ragged tile contribute exactly 0 and are never stored. At seq == 1: dq = dk = 0, dv = dout.
+ * workspace: aaclip_attention_bwd_tiled_workspace bytes (2 * batch * heads * seq floats),
+ * 16-byte aligned, as are the other operands.
+ * Replaces: the autograd of F.multi_head_attention_forward's core (model/transformer.py:200)
+ * under model/adapter.py:90-91, train.py:156.
+ */
+int aaclip_attention_bwd_tiled_workspace(int batch, int seq, int heads, size_t* bytes);
+int aaclip_attention_bwd_tiled(const float* qkv, const float* out, const float* dout, float* dqkv, int batch,
+                               int seq, int heads, int head_dim, float* workspace, size_t workspace_bytes,
+                               void* stream);
+
+/*
+ * Backward of aaclip_block_tail's level tap (tap[b, t - 1] = ln_post(x[b, t]), t >= 1): token row
+ * (b, t >= 1) of g [batch*n_tok, width] += LN_bwd(dtap[b*(n_tok-1) + t - 1]; x[b*n_tok + t], w)
+ * with aaclip_layernorm_bwd's arithmetic and w = ln_post's weight; CLS rows (t == 0) of g are
+ * not touched. x is the residual stream the tap read. g must not alias x or dtap. width 768 or
+ * 1024, n_tok >= 2.
+ * Replaces: the autograd of model/adapter.py:100-105 under train.py:156.
+ */
+int aaclip_tap_ln_bwd(const float* dtap, const float* x, const float* w, float* g, int batch, int n_tok, int width,
+                      void* stream);
+
+/*
+ * Backward of aaclip_l2_normalize, y = x / max(|x|, 1e-12) (F.normalize), one wave per row, |x|
+ * summed in the forward's order. The incoming gradient of row r is gy = scale * dy[r / dy_group]
+ * (dy_group == 0: dy[r]), so det = mean_p normalize(d_p) is one launch with dy = ddet [B, width],
+ * dy_group = P, scale = 1 / P. dx = (gy - y (y . gy)) / |x|; a row with |x| <= 1e-12 (the clamp
+ * branch, e.g. all zeros) gets gy / 1e-12. dx may be dy when dy_group == 0 (same leading
+ * dimension), never x. width 768 or 1024; ld* >= width, multiples of 4.
+ * Replaces: the autograd of model/adapter.py:109 and :111 under train.py:156.
+ */
+int aaclip_l2_normalize_bwd(const float* dy, int64_t lddy, int dy_group, float scale, const float* x, int64_t ldx,
+                            float* dx, int64_t lddx, int rows, int width, void* stream);
+
 /*
  * Full test-branch anomaly map for one batch: patch_scores (mode 0) into the
  * caller's workspace grid_ws (>= batch*g*g fp32), then blur + upsample into
