@@ -94,6 +94,9 @@ SIGNATURES = {
                                  _P],
     "aaclip_preprocess_workspace": [_I, _I, _I, _I, ctypes.POINTER(ctypes.c_size_t)],
     "aaclip_resize_masks_nearest": [_P, _L, _L, _I, _I, _I, _P, _P, _I, _P, _P],
+    "aaclip_color_jitter_workspace": [_I, ctypes.POINTER(ctypes.c_size_t)],
+    "aaclip_color_jitter_u8": [_P, _L, _L, _I, _I, _I, _P, _P, _P, ctypes.c_size_t, _P],
+    "aaclip_geom_augment": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-"""get_dataset — drop-in for reference dataset/__init__.py:175-232 (test stage).
+"""get_dataset — drop-in for reference dataset/__init__.py:175-232 (train and test stages).
 
 Test transform (reference :127-143): PIL bicubic resize to (S, S) -> [0,1]
 tensor -> CLIP mean/std normalise; masks: nearest resize -> (mask != 0).
@@ -10,7 +10,19 @@ under DATA_PATH[dataset].
 
 Extra: dataset name "synthetic" (no files needed) yields seeded N(0,1)
 post-normalisation images and rectangle masks.
-Training datasets/augmentation are out of scope.
+
+Train stage (reference :13-103, :188-202): `get_dataset(..., stage="train")` returns
+(text_dataset, image_dataset) over `<shot>-shot.jsonl` / `full-shot.jsonl`, both BaseDataset,
+the first without colour jitter (text=True). The random transforms -- ColorJitter brightness /
+contrast / saturation (p = 0.7 each), rotation within 30 degrees, translation within 15 %,
+the two flips (p = 0.5 each) -- are drawn by aaclip.preprocess.TrainPreprocessor.sample.
+raw=False items are made in the workers (Pillow's ImageEnhance and resize, the rotation through
+F.grid_sample: TrainPreprocessor.cpu_item); raw=True items carry the decoded uint8 image and
+mask and the loop runs TrainPreprocessor.apply on the device (aaclip_color_jitter_u8,
+aaclip_preprocess_images, aaclip_resize_masks_nearest, aaclip_geom_augment). The stream of
+random numbers is this build's own (one torch.rand per item or batch), not torchvision's.
+"synthetic" has a train stage too: seeded uint8 images of 96 x 80 pixels with rectangle
+masks, class names cycling through three synthetic_mvtec classes.
 
 raw=True (build extension): items carry the decoded uint8
 image [H, W, 3] and mask [H, W] instead of the transformed tensors; batch them
@@ -85,6 +97,95 @@ class BaseSingleClassDataset(Dataset):
                 "class_name": meta["class_name"]}
 
 
+class BaseDataset(Dataset):
+    """Reference dataset/__init__.py:13-103: every line of the jsonl, all classes mixed, with the
+    train-time transforms. text=True leaves the colour jitter out (stage 1). `generator` (a CPU
+    torch.Generator) drives the raw=False items' parameters; left None, one is seeded from
+    torch.initial_seed() on first use, which in a DataLoader worker is that worker's own seed."""
+
+    def __init__(self, data_path: str, meta_path: str, img_size: int, text: bool = False, raw: bool = False,
+                 generator: torch.Generator | None = None):
+        self.data_path, self.img_size, self.text, self.raw = data_path, img_size, text, raw
+        self.full_shot = "full-shot" in meta_path
+        self.generator = generator
+        self.meta = []
+        with open(meta_path) as f:
+            for line in f:
+                if line.strip():
+                    self.meta.append(json.loads(line))
+        self._prep = None
+
+    def __len__(self):
+        return len(self.meta)
+
+    def _load(self, idx):
+        """(PIL RGB image, PIL L mask or None, label, file name, class name) of item idx."""
+        from PIL import Image
+        meta = self.meta[idx]
+        img = Image.open(os.path.join(self.data_path, meta["image_path"])).convert("RGB")
+        mask = Image.open(os.path.join(self.data_path, meta["mask_path"])).convert("L") if meta["label"] else None
+        return img, mask, meta["label"], meta["image_path"], meta["class_name"]
+
+    def prep(self):
+        if self._prep is None:
+            from aaclip.preprocess import TrainPreprocessor
+            self._prep = TrainPreprocessor(self.img_size, text=self.text)
+        return self._prep
+
+    def item(self, idx, params=None):
+        """Item idx; raw=False with `params` (image 0 of a TrainPreprocessor.sample result) replays
+        those instead of drawing."""
+        img, mask, label, file_name, class_name = self._load(idx)
+        out = {"label": torch.tensor(label).to(torch.int64), "file_name": file_name, "class_name": class_name}
+        if self.raw:
+            a = np.asarray(img)
+            m = np.asarray(mask) if mask is not None else np.zeros(a.shape[:2], np.uint8)
+            return {"image_u8": torch.from_numpy(a.copy()), "mask_u8": torch.from_numpy(m.copy()), **out}
+        if params is None:
+            if self.generator is None:
+                self.generator = torch.Generator().manual_seed(torch.initial_seed() % (2 ** 63))
+            params = self.prep().sample(1, self.generator)
+        image, m = self.prep().cpu_item(img, mask, params)
+        return {"image": image, "mask": m, **out}
+
+    def __getitem__(self, idx):
+        return self.item(idx)
+
+
+class SyntheticTrainDataset(BaseDataset):
+    """Seeded synthetic train set: uint8 RGB noise images of 96 x 80 pixels (a non-square source)
+    over a smooth ramp, a rectangle mask (255) of 1-10% of the pixels in every other image, class
+    names cycling through the first three synthetic_mvtec classes."""
+    H, W = 96, 80
+
+    def __init__(self, n: int, img_size: int, text: bool = False, raw: bool = False, seed: int = 111,
+                 generator: torch.Generator | None = None):
+        self.n, self.img_size, self.text, self.raw, self.seed = n, img_size, text, raw, seed
+        self.generator, self._prep, self.full_shot = generator, None, True
+        self.classes = CLASS_NAMES["synthetic_mvtec"][:3]
+
+    def __len__(self):
+        return self.n
+
+    def _load(self, idx):
+        from PIL import Image
+        rng = np.random.Generator(np.random.Philox(key=(self.seed << 20) + idx))
+        H, W = self.H, self.W
+        ramp = np.linspace(40, 200, W)[None, :, None] + np.linspace(-30, 30, H)[:, None, None]
+        img = np.clip(ramp + rng.normal(0, 25, (H, W, 3)), 0, 255).astype(np.uint8)
+        mask = None
+        if idx % 2 == 1:
+            area = rng.uniform(0.01, 0.10) * H * W
+            h = int(max(1, min(H, round(np.sqrt(area) * rng.uniform(0.6, 1.4)))))
+            w = int(max(1, min(W, round(area / h))))
+            y, x = int(rng.integers(0, H - h + 1)), int(rng.integers(0, W - w + 1))
+            m = np.zeros((H, W), np.uint8)
+            m[y:y + h, x:x + w] = 255
+            mask = Image.fromarray(m, "L")
+        return (Image.fromarray(img, "RGB"), mask, int(mask is not None), f"synthetic/train/{idx:05d}.png",
+                self.classes[idx % len(self.classes)])
+
+
 class SyntheticSingleClassDataset(Dataset):
     """Seeded synthetic test set: N(0,1) images (already in normalised space) and
     rectangles covering 1-10% of pixels in every other image (label = mask non-empty)."""
@@ -135,8 +236,13 @@ def metadata_root() -> str:
 def get_dataset(dataset_name: str, img_size: int, training_mode: str, shot: int = -1, stage: str = "train",
                 logger=None, synthetic_n: int = 16, raw: bool = False):
     if dataset_name in ("synthetic", "synthetic_mvtec"):
+        if stage == "train":
+            if dataset_name != "synthetic":
+                raise ValueError("of the synthetic datasets only 'synthetic' has a train stage")
+            return (SyntheticTrainDataset(synthetic_n, img_size, text=True, raw=raw),
+                    SyntheticTrainDataset(synthetic_n, img_size, text=False, raw=raw))
         if stage not in ("test", "visualize"):
-            raise ValueError("the synthetic dataset only has a test stage")
+            raise ValueError(f"stage {stage} not found; available stages: train, test")
         if dataset_name == "synthetic":
             return {"bottle": SyntheticSingleClassDataset(synthetic_n, img_size)}
         # config C4's shape: every MVTec class, its own seed
@@ -145,8 +251,15 @@ def get_dataset(dataset_name: str, img_size: int, training_mode: str, shot: int 
     if "Med" not in dataset_name:
         assert dataset_name in DATA_PATH, (
             f"Dataset {dataset_name} not found; available datasets: {list(DATA_PATH.keys())}")
-    if stage == "train":
-        raise NotImplementedError("training datasets are out of scope (inference path only)")
+    if stage == "train":  # reference :188-202
+        if training_mode == "few_shot":
+            assert shot > 0, "shot should be positive"
+            meta_path = os.path.join(metadata_root(), dataset_name, f"{shot}-shot.jsonl")
+        else:
+            meta_path = os.path.join(metadata_root(), dataset_name, "full-shot.jsonl")
+        data_path = DATA_PATH[dataset_name.split("-")[0]]
+        return (BaseDataset(data_path, meta_path, img_size, text=True, raw=raw),
+                BaseDataset(data_path, meta_path, img_size, text=False, raw=raw))
     if stage in ("test", "visualize"):
         meta_path = os.path.join(metadata_root(), dataset_name, "full-shot.jsonl")
         return {c: BaseSingleClassDataset(DATA_PATH[dataset_name], meta_path, img_size, c,

@@ -17,15 +17,15 @@
       get_adapted_single_class_text_embedding's anchors carry a grad_fn through
       aaclip_anchor_reduce_bwd and the text tower's backward (TextEngine.encode_train)
       into the four text_adapter weights: train.py:62-72, :87-100 runs as written.
-      The image towers have no backward (stage 2).
+      Stage 2's backward into the image adapter is AdaptedCLIP.forward under grad.
   anomaly_map_multilevel     the fused form of test.py:86-93 (all levels in one
       stream kernel, level sum before blur+upsample).
   metrics_eval               forward_utils.py:233-280 — on device (aaclip_metrics_eval:
       min-max normalisation, score fusion, radix-sorted exact tie-aware AUROC / AP,
       identical to sklearn after the reference's 4-decimal rounding). numpy inputs
       are copied to the device; there is no CPU path (without a GPU it raises).
-FocalLoss / BinaryDiceLoss as classes with non-default arguments, the train data
-split and visualize() (cv2) are out of scope.
+FocalLoss / BinaryDiceLoss as classes with non-default arguments and visualize() (cv2)
+are out of scope.
 """
 from __future__ import annotations
 

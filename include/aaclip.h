@@ -711,6 +711,47 @@ int aaclip_resize_masks_nearest(const uint8_t* src, int64_t img_stride, int64_t 
                                 int in_h, int in_w, const int32_t* x_index, const int32_t* y_index,
                                 int out_size, float* out, void* stream);
 
+/*
+ * Train-time augmentation on the device (csrc/augment.hip). Per-image parameters are HOST
+ * arrays, validated before the first launch and passed to the kernels as arguments (64
+ * images per launch): nothing is copied, allocated or synchronised. Deterministic.
+ *
+ * Colour jitter on decoded uint8 RGB (replaces dataset/__init__.py:44-52: three
+ * RandomApply(ColorJitter(...)), which on a PIL image are ImageEnhance.Brightness, .Contrast,
+ * .Color, each Image.blend(degenerate, image, f)). src / dst: batch images [h, w, 3] with the
+ * image stride and row pitch (bytes, pitch may be padded) of aaclip_preprocess_images, the
+ * same for both; dst == src (in place) or disjoint. factors: host float [batch, 3] =
+ * brightness, contrast, saturation, applied in that order; exactly 1.0 = not applied. Per
+ * channel t = d + f * (i - d) in fp32, truncated for 0 <= f <= 1, else clipped to [0, 255]
+ * and truncated; degenerates: 0 / int(mean L + 0.5) of the image after the brightness step
+ * (exact integer sum, fp64 division) / L of the pixel, L = (19595 R + 38470 G + 7471 B +
+ * 0x8000) >> 16. Bit-exact with Pillow. workspace: 8-byte aligned device memory of
+ * aaclip_color_jitter_workspace bytes (partial sums of the contrast mean); may be NULL when
+ * every contrast factor is 1.
+ */
+int aaclip_color_jitter_workspace(int batch, size_t* bytes);
+int aaclip_color_jitter_u8(const uint8_t* src, int64_t img_stride, int64_t row_pitch, int batch, int h, int w,
+                           const float* factors, uint8_t* dst, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
+/*
+ * Geometric augmentation (replaces dataset/__init__.py:30-39, 89-94: RandomRotation(30 deg),
+ * RandomAffine(translate), RandomHorizontalFlip, RandomVerticalFlip on the fp32 cat of image
+ * and mask; nearest, fill 0) as one gather through the composed index map. src fp32
+ * [batch, channels, size, size] -> dst of the same shape; optionally a second tensor src2
+ * [batch, channels2, size, size] -> dst2 through the same map (the mask next to the image,
+ * without a cat), channels2 = 0 and NULL otherwise. No output may overlap an input.
+ * params: host int32 [batch, 5] = rotate flag, tx, ty, hflip flag, vflip flag (flags 0 / 1).
+ * cos_sin: host float [batch, 2] = cos r, sin r, r = radians(-angle) (read only with the
+ * rotate flag). For output pixel (i, j): i1 = vflip ? S-1-i : i, j1 = hflip ? S-1-j : j;
+ * (i2, j2) = (i1 - ty, j1 - tx), outside [0, S) -> 0; without rotation the source is (i2, j2),
+ * else, in fp32: xb = j2 + 0.5 - S/2, yb = i2 + 0.5 - S/2, gx = xb * (c / (0.5 S)) + yb *
+ * (s / (0.5 S)), gy = xb * (-s / (0.5 S)) + yb * (c / (0.5 S)), x = ((gx + 1) * S - 1) / 2,
+ * y likewise, source (nearbyint(y), nearbyint(x)) (halves to even), outside [0, S) -> 0.
+ */
+int aaclip_geom_augment(const float* src, const float* src2, float* dst, float* dst2, int batch, int channels,
+                        int channels2, int size, const int32_t* params, const float* cos_sin, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
