@@ -156,6 +156,10 @@ inline bool lds_attr_once(const void* fn, int bytes, unsigned& done) {
 
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
+// host-side argument checks: what a 16-B (float4) / 4-B access of the pointer needs
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
+
 // ---------------------------------------------------------------- step timeline (diagnostic)
 // Built only with -DAACLIP_TRACE (`make trace` -> libaaclip_hip_trace.so; the product
 // library compiles none of this): every wave of an instrumented kernel appends one

@@ -5,23 +5,17 @@
 // HBM-bound streaming work. One wave (64 lanes) owns one row of width
 // 256*VEC (768 -> VEC 3, 1024 -> VEC 4); lane l holds elements 256c + 4l .. +3,
 // so every load/store instruction moves one contiguous 1 KiB (fp32) or 512 B
-// (bf16) segment of the row. Mean/variance/norms are wave-shuffle reductions.
+// (bf16) segment of the row. Mean/variance/norms are wave-shuffle reductions
+// (rowmath.h: the fp32 row helpers shared with the backward kernels).
 #include "common.h"
+#include "rowmath.h"
 
 namespace {
-
-constexpr float kLnEps = 1e-5f;  // nn.LayerNorm default (transformer.py:37-43)
-
-template <int VEC>
-__device__ __forceinline__ void load_f32(const float* p, float4_t (&v)[VEC], int lane) {
-#pragma unroll
-  for (int c = 0; c < VEC; ++c) v[c] = *(const float4_t*)(p + 256 * c + 4 * lane);
-}
 
 template <int VEC>
 __device__ __forceinline__ void load_any(const void* p, int dtype, float4_t (&v)[VEC], int lane) {
   if (dtype == AACLIP_F32) {
-    load_f32<VEC>((const float*)p, v, lane);
+    load_row<VEC>((const float*)p, v, lane);
   } else if (dtype == AACLIP_F16) {
     const uint16_t* q = (const uint16_t*)p;
 #pragma unroll
@@ -48,8 +42,7 @@ __device__ __forceinline__ void load_any(const void* p, int dtype, float4_t (&v)
 template <int VEC>
 __device__ __forceinline__ void store_any(void* p, int dtype, const float4_t (&v)[VEC], int lane) {
   if (dtype == AACLIP_F32) {
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) *(float4_t*)((float*)p + 256 * c + 4 * lane) = v[c];
+    store_row<VEC>((float*)p, v, lane);
   } else {
     const bool h = dtype == AACLIP_F16;
     uint16_t* q = (uint16_t*)p;
@@ -63,34 +56,11 @@ __device__ __forceinline__ void store_any(void* p, int dtype, const float4_t (&v
   }
 }
 
-template <int VEC>
-__device__ __forceinline__ float row_sumsq(const float4_t (&v)[VEC]) {
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < VEC; ++c)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s += v[c][j] * v[c][j];
-  return wave_sum(s);
-}
-
 // F.layer_norm: (x - mean) / sqrt(var + eps) * w + b, biased variance.
 template <int VEC>
 __device__ __forceinline__ void layer_norm(const float4_t (&x)[VEC], const float* w, const float* b,
                                            float4_t (&y)[VEC], int lane) {
-  constexpr float inv_d = 1.0f / (256 * VEC);
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < VEC; ++c) s += (x[c][0] + x[c][1]) + (x[c][2] + x[c][3]);
-  const float mean = wave_sum(s) * inv_d;
-  float q = 0.f;
-#pragma unroll
-  for (int c = 0; c < VEC; ++c)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float d = x[c][j] - mean;
-      q += d * d;
-    }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) * inv_d + kLnEps);
+  const auto [mean, rstd] = ln_stats<VEC>(x);
 #pragma unroll
   for (int c = 0; c < VEC; ++c) {
     float4_t wv = *(const float4_t*)(w + 256 * c + 4 * lane);
@@ -160,8 +130,8 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(int out_dtype, float* x, 
   const int t = row % n_tok;
   float* xr = x + (size_t)row * D;
   float4_t e[VEC], p[VEC];
-  load_f32<VEC>(t == 0 ? cls : xr, e, lane);
-  load_f32<VEC>(pos + (size_t)t * D, p, lane);
+  load_row<VEC>(t == 0 ? cls : xr, e, lane);
+  load_row<VEC>(pos + (size_t)t * D, p, lane);
 #pragma unroll
   for (int c = 0; c < VEC; ++c) e[c] += p[c];
   float4_t y[VEC];
@@ -185,13 +155,13 @@ __global__ __launch_bounds__(256) void block_tail_kernel(int out_dtype, float* x
   constexpr int D = 256 * VEC;
   float* xr = x + (size_t)row * D;
   float4_t v[VEC];
-  load_f32<VEC>(xr, v, lane);
+  load_row<VEC>(xr, v, lane);
   if (u) {
     // adapter.py:94-99: u * ||x|| / ||u||, then w*u + (1-w)*x
     float4_t a[VEC];
-    load_f32<VEC>(u + (size_t)row * D, a, lane);
-    const float xn = sqrtf(row_sumsq<VEC>(v));
-    const float un = sqrtf(row_sumsq<VEC>(a));
+    load_row<VEC>(u + (size_t)row * D, a, lane);
+    const float xn = sqrtf(row_dot<VEC>(v, v));
+    const float un = sqrtf(row_dot<VEC>(a, a));
     const float keep = 1.0f - aw;
 #pragma unroll
     for (int c = 0; c < VEC; ++c)
@@ -224,7 +194,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(int out_dtype, const flo
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   float4_t v[VEC], o[VEC];
-  load_f32<VEC>(x + (size_t)row * ldx, v, lane);
+  load_row<VEC>(x + (size_t)row * ldx, v, lane);
   layer_norm<VEC>(v, w, b, o, lane);
   if (out_dtype == AACLIP_FP8)
     store_mx<VEC>((uint8_t*)y, sc, ld_sc, row, o, lane);  // ldy == width (checked on the host)
@@ -244,8 +214,8 @@ __global__ __launch_bounds__(256) void text_embed_ln_kernel(int out_dtype, const
   const int t = row % ctx;
   const int tok = tokens[row];
   float4_t e[VEC], p[VEC];
-  load_f32<VEC>(temb + (size_t)tok * D, e, lane);
-  load_f32<VEC>(pos + (size_t)t * D, p, lane);
+  load_row<VEC>(temb + (size_t)tok * D, e, lane);
+  load_row<VEC>(pos + (size_t)t * D, p, lane);
 #pragma unroll
   for (int c = 0; c < VEC; ++c) e[c] += p[c];
   store_any<VEC>(x + (size_t)row * D, AACLIP_F32, e, lane);
@@ -275,7 +245,7 @@ __global__ __launch_bounds__(256) void eot_ln_kernel(int out_dtype, const float*
     if (ov > best_v || (ov == best_v && oi < best_i)) { best_v = ov; best_i = oi; }
   }
   float4_t v[VEC], o[VEC];
-  load_f32<VEC>(x + ((size_t)s * ctx + best_i) * D, v, lane);
+  load_row<VEC>(x + ((size_t)s * ctx + best_i) * D, v, lane);
   layer_norm<VEC>(v, w, b, o, lane);
   store_any<VEC>((char*)y + (size_t)s * D * esize(out_dtype), out_dtype, o, lane);
 }
@@ -289,7 +259,7 @@ __global__ __launch_bounds__(256) void l2norm_kernel(int in_dtype, int out_dtype
   if (row >= rows) return;
   float4_t v[VEC];
   load_any<VEC>((const char*)x + (size_t)row * ldx * esize(in_dtype), in_dtype, v, lane);
-  const float inv = 1.0f / fmaxf(sqrtf(row_sumsq<VEC>(v)), 1e-12f);
+  const float inv = 1.0f / fmaxf(sqrtf(row_dot<VEC>(v, v)), 1e-12f);
 #pragma unroll
   for (int c = 0; c < VEC; ++c) v[c] = v[c] * inv;
   store_any<VEC>((char*)y + (size_t)row * ldy * esize(out_dtype), out_dtype, v, lane);
@@ -421,13 +391,6 @@ __global__ __launch_bounds__(256) void im2col_kernel(int out_dtype, const float*
     *(uint4*)((uint16_t*)cols + row * kp + kc * 8) = r;
   }
 }
-
-#define DISPATCH_VEC(width, ...)                 \
-  switch ((width)) {                             \
-    case 768: { constexpr int V = 3; __VA_ARGS__; break; } \
-    case 1024: { constexpr int V = 4; __VA_ARGS__; break; } \
-    default: return AACLIP_ERR_ARG;              \
-  }
 
 inline bool dtype_ok(int d) { return d == AACLIP_F32 || d == AACLIP_BF16 || d == AACLIP_F16; }
 // fp8 MX outputs (config C5) need the e8m0 scale buffer [width/128][ld_mx >= rows][2]

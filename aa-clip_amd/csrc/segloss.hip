@@ -352,9 +352,6 @@ __global__ __launch_bounds__(256) void patch_logits_bwd_finalize_kernel(const fl
   dT[(size_t)blockIdx.y * 1536 + e] = (float)(100.0 * t);
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
-
 // S * S and batch * 2 * S * S as ints the kernels index with size_t; the grid's y / z
 // dimensions take the batch (<= 65535).
 bool image_dims_ok(int batch, int out_size) {

@@ -8,74 +8,9 @@
 // kernels are written for clarity and exactness, not for throughput; the input-gradient
 // GEMMs around them are the existing aaclip_gemm on transposed weight copies.
 #include "common.h"
+#include "rowmath.h"  // the row layout, the LayerNorm statistics and layer_norm_bwd, shared with rows.hip
 
 namespace {
-
-constexpr float kLnEps = 1e-5f;  // as rows.hip (nn.LayerNorm default)
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-bool aligned4(const void* p) { return ((uintptr_t)p & 3) == 0; }
-
-// lane l of a wave owns elements 256 c + 4 l .. + 3 of a row of 256 * VEC (rows.hip layout)
-template <int VEC>
-__device__ __forceinline__ void load_row(const float* p, float4_t (&v)[VEC], int lane) {
-#pragma unroll
-  for (int c = 0; c < VEC; ++c) v[c] = *(const float4_t*)(p + 256 * c + 4 * lane);
-}
-template <int VEC>
-__device__ __forceinline__ void store_row(float* p, const float4_t (&v)[VEC], int lane) {
-#pragma unroll
-  for (int c = 0; c < VEC; ++c) *(float4_t*)(p + 256 * c + 4 * lane) = v[c];
-}
-template <int VEC>
-__device__ __forceinline__ float row_dot(const float4_t (&a)[VEC], const float4_t (&b)[VEC]) {
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < VEC; ++c)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s += a[c][j] * b[c][j];
-  return wave_sum(s);
-}
-
-// dx = d LN(x; w) / dx applied to dy: mean / rstd recomputed as rows.hip's layer_norm does,
-// g = dy w, xh = (x - mean) rstd, dx = rstd (g - mean(g) - xh mean(g xh)).
-template <int VEC>
-__device__ __forceinline__ void layer_norm_bwd(const float4_t (&x)[VEC], const float4_t (&dy)[VEC], const float* w,
-                                               float4_t (&dx)[VEC], int lane) {
-  constexpr float inv_d = 1.0f / (256 * VEC);
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < VEC; ++c) s += (x[c][0] + x[c][1]) + (x[c][2] + x[c][3]);
-  const float mean = wave_sum(s) * inv_d;
-  float q = 0.f;
-#pragma unroll
-  for (int c = 0; c < VEC; ++c)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float d = x[c][j] - mean;
-      q += d * d;
-    }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) * inv_d + kLnEps);
-  float4_t g[VEC], xh[VEC];
-  float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int c = 0; c < VEC; ++c) {
-    const float4_t wv = *(const float4_t*)(w + 256 * c + 4 * lane);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      g[c][j] = dy[c][j] * wv[j];
-      xh[c][j] = (x[c][j] - mean) * rstd;
-      s1 += g[c][j];
-      s2 += g[c][j] * xh[c][j];
-    }
-  }
-  s1 = wave_sum(s1) * inv_d;
-  s2 = wave_sum(s2) * inv_d;
-#pragma unroll
-  for (int c = 0; c < VEC; ++c)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) dx[c][j] = rstd * (g[c][j] - s1 - xh[c][j] * s2);
-}
 
 // ------------------------------------------------------------------ attention backward
 // One workgroup of 4 waves per (sequence, head). q, k, v, dout tiles [seq][64] (row pitch
@@ -259,7 +194,7 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(int mode, const float* dy,
 // y = w u |x| / |u| + (1 - w) x (block_tail_kernel; adapter.py:131-136), a = sum dy u:
 //   dx = (1 - w) dy + w (a / |u|) x / |x|         (the direct path and the path through |x|)
 //   du = w (|x| / |u|) (dy - u a / |u|^2)
-// Norms are sqrt(row_sumsq) in the forward's summation order.
+// Norms are sqrt(row_dot(x, x)), the forward's own call.
 template <int VEC>
 __global__ __launch_bounds__(256) void adapter_blend_bwd_kernel(const float* dy, const float* __restrict__ x,
                                                                 const float* __restrict__ u, float aw, float* dx,
@@ -416,13 +351,6 @@ __global__ __launch_bounds__(256) void linear_wgrad_finalize_kernel(const float*
   for (int c = 0; c < nchunk; ++c) s += (double)partial[(size_t)c * nk + e];
   dW[(e / K) * lddw + e % K] = (float)s;
 }
-
-#define DISPATCH_VEC(width, ...)                            \
-  switch ((width)) {                                        \
-    case 768: { constexpr int V = 3; __VA_ARGS__; break; }  \
-    case 1024: { constexpr int V = 4; __VA_ARGS__; break; } \
-    default: return AACLIP_ERR_ARG;                         \
-  }
 
 bool act_mode_ok(int mode) { return mode == AACLIP_EPI_GELU || mode == AACLIP_EPI_QGELU || mode == AACLIP_EPI_LEAKY; }
 

@@ -6,33 +6,9 @@
 // All fp32, deterministic (no floating-point atomics, fixed reduction orders: two launches
 // give the same bits) and image / row local.
 #include "common.h"
+#include "rowmath.h"  // the row layout, the LayerNorm statistics and layer_norm_bwd, shared with rows.hip
 
 namespace {
-
-constexpr float kLnEps = 1e-5f;  // as rows.hip (nn.LayerNorm default)
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// lane l of a wave owns elements 256 c + 4 l .. + 3 of a row of 256 * VEC (rows.hip layout)
-template <int VEC>
-__device__ __forceinline__ void load_row(const float* p, float4_t (&v)[VEC], int lane) {
-#pragma unroll
-  for (int c = 0; c < VEC; ++c) v[c] = *(const float4_t*)(p + 256 * c + 4 * lane);
-}
-template <int VEC>
-__device__ __forceinline__ void store_row(float* p, const float4_t (&v)[VEC], int lane) {
-#pragma unroll
-  for (int c = 0; c < VEC; ++c) *(float4_t*)(p + 256 * c + 4 * lane) = v[c];
-}
-template <int VEC>
-__device__ __forceinline__ float row_dot(const float4_t (&a)[VEC], const float4_t (&b)[VEC]) {
-  float s = 0.f;
-#pragma unroll
-  for (int c = 0; c < VEC; ++c)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) s += a[c][j] * b[c][j];
-  return wave_sum(s);
-}
 
 // ------------------------------------------------------------------ tiled attention backward
 // fp32 on v_mfma_f32_16x16x4f32, non-causal, head_dim 64, any sequence length. With
@@ -327,9 +303,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------ level tap + ln_post backward
-// Token row (b, t >= 1) of g += LN_bwd(dtap[b, t - 1]; x[b, t], w): text_bwd.hip's LayerNorm
-// backward arithmetic (mean / rstd recomputed as rows.hip's layer_norm does). CLS rows return
-// before they touch memory. One wave per token row.
+// Token row (b, t >= 1) of g += LN_bwd(dtap[b, t - 1]; x[b, t], w) (layer_norm_bwd, rowmath.h).
+// CLS rows return before they touch memory. One wave per token row.
 template <int VEC>
 __global__ __launch_bounds__(256) void tap_ln_bwd_kernel(const float* __restrict__ dtap, const float* __restrict__ x,
                                                          const float* __restrict__ w, float* __restrict__ g, int rows,
@@ -340,49 +315,19 @@ __global__ __launch_bounds__(256) void tap_ln_bwd_kernel(const float* __restrict
   const int tk = row % n_tok;
   if (tk == 0) return;
   constexpr int D = 256 * VEC;
-  constexpr float inv_d = 1.0f / D;
   const size_t trow = (size_t)(row / n_tok) * (n_tok - 1) + (tk - 1);
-  float4_t xv[VEC], dy[VEC], gv[VEC];
+  float4_t xv[VEC], dy[VEC], gv[VEC], o[VEC];
   load_row<VEC>(x + (size_t)row * D, xv, lane);
   load_row<VEC>(dtap + trow * D, dy, lane);
   load_row<VEC>(g + (size_t)row * D, gv, lane);
-  float s = 0.f;
+  layer_norm_bwd<VEC>(xv, dy, w, o, lane);
 #pragma unroll
-  for (int c = 0; c < VEC; ++c) s += (xv[c][0] + xv[c][1]) + (xv[c][2] + xv[c][3]);
-  const float mean = wave_sum(s) * inv_d;
-  float q = 0.f;
-#pragma unroll
-  for (int c = 0; c < VEC; ++c)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float d = xv[c][j] - mean;
-      q += d * d;
-    }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) * inv_d + kLnEps);
-  float4_t gw[VEC], xh[VEC];
-  float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int c = 0; c < VEC; ++c) {
-    const float4_t wv = *(const float4_t*)(w + 256 * c + 4 * lane);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      gw[c][j] = dy[c][j] * wv[j];
-      xh[c][j] = (xv[c][j] - mean) * rstd;
-      s1 += gw[c][j];
-      s2 += gw[c][j] * xh[c][j];
-    }
-  }
-  s1 = wave_sum(s1) * inv_d;
-  s2 = wave_sum(s2) * inv_d;
-#pragma unroll
-  for (int c = 0; c < VEC; ++c)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) gv[c][j] = gv[c][j] + rstd * (gw[c][j] - s1 - xh[c][j] * s2);
-  store_row<VEC>(g + (size_t)row * D, gv, lane);
+  for (int c = 0; c < VEC; ++c) o[c] = gv[c] + o[c];
+  store_row<VEC>(g + (size_t)row * D, o, lane);
 }
 
 // ------------------------------------------------------------------ L2-normalise backward
-// y = x / max(|x|, 1e-12) (l2norm_kernel; |x| = sqrt(row_sumsq) in its summation order). With
+// y = x / max(|x|, 1e-12) (l2norm_kernel; |x| = sqrt(row_dot(x, x)), its own call). With
 // gy = scale * dy[row / group] (group 0: dy[row]):
 //   |x| >  1e-12:  dx = (gy - y (y . gy)) / |x|
 //   |x| <= 1e-12:  dx = gy / 1e-12                 (the clamp passes no gradient to the norm)
@@ -415,13 +360,6 @@ __global__ __launch_bounds__(256) void l2_normalize_bwd_kernel(const float* dy, 
   }
   store_row<VEC>(dx + (size_t)row * lddx, o, lane);  // dx may be dy (group 0): read above, by the same lane
 }
-
-#define DISPATCH_VEC(width, ...)                            \
-  switch ((width)) {                                        \
-    case 768: { constexpr int V = 3; __VA_ARGS__; break; }  \
-    case 1024: { constexpr int V = 4; __VA_ARGS__; break; } \
-    default: return AACLIP_ERR_ARG;                         \
-  }
 
 }  // namespace
 

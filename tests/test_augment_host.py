@@ -28,7 +28,7 @@ def test_entries_are_declared_and_bound():
     for name in NEW:
         assert re.search(r"\bint\s+%s\s*\(" % name, src), name
         assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert _lib.ABI_VERSION == 8 and lib.aaclip_abi_version() == 8
+    assert _lib.ABI_VERSION == 9 and lib.aaclip_abi_version() == 9
     # each cites the reference lines it replaces
     assert "dataset/__init__.py:44-52" in src and "dataset/__init__.py:30-39, 89-94" in src
 

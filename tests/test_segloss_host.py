@@ -32,7 +32,7 @@ def test_abi_8_declares_binds_and_exports_the_six_entry_points():
     for name in NEW:
         assert re.search(r"\bint " + name + r"\(", src), name
         assert name in _lib.SIGNATURES and hasattr(lib, name), name
-    assert _lib.ABI_VERSION == 8 and lib.aaclip_abi_version() == 8
+    assert _lib.ABI_VERSION == 9 and lib.aaclip_abi_version() == 9
     for cite in ("forward_utils.py:21-126", "199-202", "211-215", "forward_utils.py:219-227", "train.py:86-100"):
         assert cite in src, cite
     # argument counts follow the header

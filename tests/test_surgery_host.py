@@ -93,9 +93,9 @@ def test_abi_8_declares_binds_and_exports_vv_attention():
     assert re.search(r"#define AACLIP_VV_MAX_BATCH 64\b", src)
     assert "transformer.py:125-152" in src and "407-425" in src
     assert "aaclip_vv_attention" in _lib.SIGNATURES and len(_lib.SIGNATURES["aaclip_vv_attention"]) == 10
-    assert _lib.ABI_VERSION == 8 and _lib.VV_MAX_BATCH == 64
+    assert _lib.ABI_VERSION == 9 and _lib.VV_MAX_BATCH == 64
     lib = _lib.lib()
-    assert lib.aaclip_abi_version() == 8 and hasattr(lib, "aaclip_vv_attention")
+    assert lib.aaclip_abi_version() == 9 and hasattr(lib, "aaclip_vv_attention")
 
 
 def test_vv_attention_rejects_bad_arguments_without_a_launch():

@@ -36,7 +36,7 @@ def test_abi_8_declares_binds_and_exports_the_text_backward():
         assert name in _lib.SIGNATURES and hasattr(lib, name), name
         decl = re.search(r"\bint " + name + r"\(([^;]*)\);", src).group(1)
         assert len(decl.split(",")) == len(_lib.SIGNATURES[name]), name
-    assert _lib.ABI_VERSION == 8 and lib.aaclip_abi_version() == 8
+    assert _lib.ABI_VERSION == 9 and lib.aaclip_abi_version() == 9
     for cite in ("model/adapter.py:125-128", "model/adapter.py:130-136", "model/adapter.py:138-140",
                  "forward_utils.py:155-159", "transformer.py:46-49", "model/adapter_modules.py:6-47", "train.py:99"):
         assert cite in src, cite

@@ -9,7 +9,7 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 B=/tmp/aaclip_ab_build/$NAME
 mkdir -p "$B" "$R/ab"
 cd "$R/aa-clip_amd/csrc"
-FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -Wno-unused-function -munsafe-fp-atomics -I../../include"
+FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -Wno-unused-function -I../../include"
 for f in gemm attention rows anomaly_map metrics preprocess version; do
   extra=""
   [ $f = attention ] && extra=-fno-honor-nans
