@@ -80,6 +80,150 @@ def _quant_weight_fp8(w: torch.Tensor):
     return (w / s[:, None]).to(FP8).contiguous(), s.contiguous()
 
 
+# ---------------------------------------------------------------------- packing (all engines)
+def _to(t: torch.Tensor, dev, dtype):
+    return t.detach().to(dev, dtype).contiguous()
+
+
+def _pack_block(params: dict, p: str, dev, dtype, **in_proj):
+    """The block dict of `p` = "...resblocks.{i}.": LayerNorm pairs and biases fp32, GEMM weights
+    in `dtype`, nn.Linear [N, K] layout kept. in_proj = the packed in-projection pair under the
+    caller's key names (the Q fold and the surgery blocks' V-rows slice are the caller's)."""
+    f32 = lambda k: _to(params[p + k], dev, torch.float32)  # noqa: E731
+    cdt = lambda k: _to(params[p + k], dev, dtype)  # noqa: E731
+    return dict(
+        ln1=(f32("ln_1.weight"), f32("ln_1.bias")), ln2=(f32("ln_2.weight"), f32("ln_2.bias")), **in_proj,
+        w_o=cdt("attn.out_proj.weight"), b_o=f32("attn.out_proj.bias"),
+        w_fc=cdt("mlp.c_fc.weight"), b_fc=f32("mlp.c_fc.bias"),
+        w_pr=cdt("mlp.c_proj.weight"), b_pr=f32("mlp.c_proj.bias"),
+    )
+
+
+def _pack_visual_stem(vparams: dict, dev, dtype):
+    """(conv, cls, pos, ln_pre, ln_post) of a visual tower: conv1 flattened to [1024, 640] in
+    `dtype` (K padded 588 -> 640 with zeros), the embeddings and LayerNorm pairs fp32."""
+    f32 = lambda k: _to(vparams["visual." + k], dev, torch.float32)  # noqa: E731
+    w = vparams["visual.conv1.weight"].detach().reshape(WIDTH, -1)
+    conv = torch.zeros(WIDTH, KPATCH, device=dev, dtype=torch.float32)
+    conv[:, : w.shape[1]] = w
+    return (conv.to(dtype).contiguous(), f32("class_embedding"), f32("positional_embedding"),
+            (f32("ln_pre.weight"), f32("ln_pre.bias")), (f32("ln_post.weight"), f32("ln_post.bias")))
+
+
+def _check_image(x: torch.Tensor):
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[2] % PATCH:
+        raise ValueError("input must be [B, 3, S, S] with S a multiple of 14")
+
+
+def _check_pos(pos: torch.Tensor, n_tok: int):
+    if pos.shape[0] != n_tok:
+        raise ValueError(f"positional embedding has {pos.shape[0]} rows, image needs {n_tok} "
+                         "(resize it at load time, reference model/model.py:395-426)")
+
+
+# ---------------------------------------------------------------------- training (both towers)
+def _check_adapter_weights(ws: list, shapes: list, device):
+    """ws: the adapter weights of a training call, shapes: the shape each must have."""
+    if len(ws) != len(shapes):
+        raise ValueError(f"expected {len(shapes)} adapter weights, got {len(ws)}")
+    for i, (w, want) in enumerate(zip(ws, shapes)):
+        if w.device != device or w.dtype != torch.float32 or tuple(w.shape) != want or not w.is_contiguous():
+            raise ValueError(f"adapter weight {i} must be a contiguous fp32 {list(want)} tensor on {device}")
+
+
+def _lowest_trainable(need, adapt_until: int):
+    """Index of the lowest layer adapter whose weight needs a gradient (None: none does)."""
+    return next((i for i in range(adapt_until) if need[i]), None)
+
+
+def _bwd_weights(blocks: list, upto: int):
+    """W^T copies of the frozen weights of blocks 1..upto-1: dX = dY . W is aaclip_gemm
+    (C = A . W'^T) with W' = W^T. Packed once per engine, on the first training call; block 0
+    never needs a backward (no trainable weight lies below the adapter that follows it)."""
+    tr = lambda w: w.t().contiguous()  # noqa: E731
+    return [None] + [dict(w_qkv=tr(b["w_qkv"]), w_o=tr(b["w_o"]), w_fc=tr(b["w_fc"]), w_pr=tr(b["w_pr"]))
+                     for b in blocks[1:upto]]
+
+
+def _train_block_fwd(blk: dict, X, H, scratch, attend, *, keep: bool, keep_blend: bool, keep_att: bool, act,
+                     w_adapt, saved: dict, i: int):
+    """Block i of a training forward in fp32, from the QKV GEMM through c_proj and the adapter
+    GEMM (w_adapt, or None): the inference block's launches. X: the residual stream, H: ln_1(X)
+    on entry; scratch = (qkv, att, fc, u), what a block without a backward writes;
+    attend(qkv, att) launches the tower's attention. keep: the block has a backward, so it
+    writes fresh buffers, filed under saved[i], with c_fc's pre-activation kept (aaclip_gemm
+    bias-only + aaclip_act: the epilogue's own device function); keep_att: att among them (the
+    attention backward reads the forward's output). keep_blend: so has the adapter after it.
+    Returns (X, u) for the caller's block tail; u = LeakyReLU(adapter(X)), or None."""
+    R, W = X.shape
+    e = lambda *s: torch.empty(*s, device=X.device, dtype=torch.float32)  # noqa: E731
+    qkv, att, fc, u = scratch
+    fc_pre = fc
+    if keep:
+        qkv = e(R, 3 * W)
+        if keep_att:
+            att = e(R, W)
+        fc_pre = e(R, 4 * W)
+    ops.gemm(H, blk["w_qkv"], qkv, bias=blk["b_qkv"])
+    attend(qkv, att)
+    x_in = X
+    x_mid = e(R, W) if keep else X
+    ops.gemm(att, blk["w_o"], x_mid, bias=blk["b_o"], residual=x_in)
+    ops.layernorm(x_mid, blk["ln2"][0], blk["ln2"][1], H)
+    if keep:
+        ops.gemm(H, blk["w_fc"], fc_pre, bias=blk["b_fc"])
+        ops.act(fc_pre, act, out=fc)
+    else:
+        ops.gemm(H, blk["w_fc"], fc, bias=blk["b_fc"], gelu=act)
+    X = e(R, W) if (keep or keep_blend) else x_mid
+    ops.gemm(fc, blk["w_pr"], X, bias=blk["b_pr"], residual=x_mid)
+    if keep:
+        saved[i] = dict(x_in=x_in, qkv=qkv, x_mid=x_mid, fc_pre=fc_pre)
+        if keep_att:
+            saved[i]["att"] = att
+    if w_adapt is None:
+        return X, None
+    if keep_blend:
+        u = e(R, W)
+    ops.gemm(X, w_adapt, u, leaky=True)
+    if keep_blend:  # the blend is in place: keep the pre-blend x, blend a copy
+        saved.setdefault(i, {}).update(x_pre=X, u=u)
+        X = X.clone()
+    return X, u
+
+
+def _blend_bwd(i: int, lowest: int, g, du, sv: dict, ws: list, adapt_weight: float, need, grads: list, taps):
+    """g = dL/d(x after block i, blended) -> dL/d(block i's own output), in place; sv: the
+    block's saved dict (no "u": no trainable adapter follows it and g passes through). Fills
+    grads[i] where need[i] asks; at block `lowest` the walk ends and the adapter path's dx is
+    not added. taps: the tap_blocks diagnostic's dict when it wants block i, else None."""
+    wt = lambda w: w.detach().t().contiguous()  # noqa: E731
+    if "u" in sv:  # x <- w u |x| / |u| + (1 - w) x after block i, u = LeakyReLU(x Wa_i^T)
+        ops.adapter_blend_bwd(g, sv["x_pre"], sv["u"], adapt_weight, dx=g, du=du)
+        ops.act_bwd(du, sv["u"], "leaky", out=du)
+        if need[i]:
+            grads[i] = ops.linear_wgrad(du, sv["x_pre"])
+        if i > lowest:
+            ops.gemm(du, wt(ws[i]), g, residual=g)
+    if taps is not None:  # diagnostic: dL/d(block i's own output), the adapter path included
+        taps[i] = g.clone() if i > lowest else ops.gemm(du, wt(ws[i]), torch.empty_like(g), residual=g)
+
+
+def _block_bwd(g, blk: dict, bt: dict, sv: dict, attend_bwd, act_mode: str, d_qkv, d_wide, d_w):
+    """g = dL/d(block output) -> dL/d(block input), in place, through the frozen block: the
+    input-gradient GEMMs on the transposed weights bt (_bwd_weights), no weight gradient.
+    attend_bwd(sv, d_att, d_qkv) launches the tower's attention backward; d_qkv / d_wide /
+    d_w are [R, 3W] / [R, 4W] / [R, W] scratch."""
+    ops.gemm(g, bt["w_pr"], d_wide)                                        # 1. d_act = g . W_pr
+    ops.act_bwd(d_wide, sv["fc_pre"], act_mode, out=d_wide)                # 2. d_pre = d_act gelu'(fc_pre)
+    ops.gemm(d_wide, bt["w_fc"], d_w)                                      # 3. d_h2 = d_pre . W_fc
+    ops.layernorm_bwd(d_w, sv["x_mid"], blk["ln2"][0], residual=g, out=g)  # 4. g_mid
+    ops.gemm(g, bt["w_o"], d_w)                                            # 5. d_att = g_mid . W_o
+    attend_bwd(sv, d_w, d_qkv)                                             # 6. d_qkv
+    ops.gemm(d_qkv, bt["w_qkv"], d_w)                                      # 7. d_h1 = d_qkv . W_qkv
+    ops.layernorm_bwd(d_w, sv["x_in"], blk["ln1"][0], residual=g, out=g)   # 8. g_in
+
+
 class VisualEngine:
     def __init__(self, vparams: dict, adapter: dict, *, levels=(6, 12, 18, 24), image_adapt_until=6,
                  image_adapt_weight=0.1, dtype=torch.bfloat16, fold_q_scale=True, fp8_scope="mlp",
@@ -116,16 +260,7 @@ class VisualEngine:
         if dev.type != "cuda":
             raise RuntimeError("VisualEngine needs device tensors (no CPU path)")
         self.device = dev
-        f32 = lambda t: t.detach().to(dev, torch.float32).contiguous()  # noqa: E731
-        cdt = lambda t: t.detach().to(dev, dtype).contiguous()  # noqa: E731
-        w = vparams["visual.conv1.weight"].detach().reshape(WIDTH, -1)
-        conv = torch.zeros(WIDTH, KPATCH, device=dev, dtype=torch.float32)
-        conv[:, : w.shape[1]] = w
-        self.conv = conv.to(dtype).contiguous()
-        self.cls = f32(vparams["visual.class_embedding"])
-        self.pos = f32(vparams["visual.positional_embedding"])
-        self.ln_pre = (f32(vparams["visual.ln_pre.weight"]), f32(vparams["visual.ln_pre.bias"]))
-        self.ln_post = (f32(vparams["visual.ln_post.weight"]), f32(vparams["visual.ln_post.bias"]))
+        self.conv, self.cls, self.pos, self.ln_pre, self.ln_post = _pack_visual_stem(vparams, dev, dtype)
         # bf16/fp8: the attention softmax runs in the log2 domain on q' = q * log2(e)/8;
         # the factor is folded into the Q rows of in_proj (weights and bias, in fp32
         # before the bf16/e4m3 rounding), so no per-score scaling remains in the kernel
@@ -140,15 +275,9 @@ class VisualEngine:
         self.blocks = []
         for i in range(LAYERS):
             p = f"visual.transformer.resblocks.{i}."
-            self.blocks.append(dict(
-                ln1=(f32(vparams[p + "ln_1.weight"]), f32(vparams[p + "ln_1.bias"])),
-                ln2=(f32(vparams[p + "ln_2.weight"]), f32(vparams[p + "ln_2.bias"])),
-                w_qkv=cdt(qkv_param(vparams[p + "attn.in_proj_weight"])),
-                b_qkv=qkv_param(vparams[p + "attn.in_proj_bias"]),
-                w_o=cdt(vparams[p + "attn.out_proj.weight"]), b_o=f32(vparams[p + "attn.out_proj.bias"]),
-                w_fc=cdt(vparams[p + "mlp.c_fc.weight"]), b_fc=f32(vparams[p + "mlp.c_fc.bias"]),
-                w_pr=cdt(vparams[p + "mlp.c_proj.weight"]), b_pr=f32(vparams[p + "mlp.c_proj.bias"]),
-            ))
+            self.blocks.append(_pack_block(vparams, p, dev, dtype,
+                                           w_qkv=_to(qkv_param(vparams[p + "attn.in_proj_weight"]), dev, dtype),
+                                           b_qkv=qkv_param(vparams[p + "attn.in_proj_bias"])))
         if self.fp8:  # e4m3 copies of the block GEMM weights (the bf16 copies are dropped)
             for blk in self.blocks:
                 for k in (("w_fc", "w_pr") if self.fp8_mlp_only else ("w_qkv", "w_o", "w_fc", "w_pr")):
@@ -188,16 +317,6 @@ class VisualEngine:
         self._graph_cache, self._last_key = {}, None
 
     # ------------------------------------------------------------------ training (stage 2)
-    def _bwd_weights(self):
-        """W^T copies of the frozen block weights: dX = dY . W is aaclip_gemm (C = A . W'^T)
-        with W' = W^T. Packed once per engine, on the first training call; block 0 never
-        needs a backward (no trainable weight lies below the adapter that follows it)."""
-        if self._bwd is None:
-            tr = lambda w: w.t().contiguous()  # noqa: E731
-            self._bwd = [None] + [dict(w_qkv=tr(b["w_qkv"]), w_o=tr(b["w_o"]), w_fc=tr(b["w_fc"]), w_pr=tr(b["w_pr"]))
-                                  for b in self.blocks[1:self.levels[-1]]]
-        return self._bwd
-
     def forward_train(self, x: torch.Tensor, adapter_weights):
         """forward() with a grad_fn into the image adapter (stage 2, reference train.py:117-174).
         adapter_weights: the adapt_until layer-adapter weights [1024, 1024], one seg_proj weight
@@ -210,14 +329,8 @@ class VisualEngine:
             raise RuntimeError("the visual tower trains in fp32 only")
         ws = list(adapter_weights)
         L = len(self.levels)
-        if len(ws) != self.adapt_until + L + 1:
-            raise ValueError(f"expected {self.adapt_until + L + 1} adapter weights, got {len(ws)}")
-        for i, w in enumerate(ws):
-            want = (WIDTH, WIDTH) if i < self.adapt_until else (EMBED, WIDTH)
-            if w.device != self.device or w.dtype != torch.float32 or tuple(w.shape) != want or not w.is_contiguous():
-                raise ValueError(f"adapter weight {i} must be a contiguous fp32 {list(want)} tensor on {self.device}")
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[2] % PATCH:
-            raise ValueError("input must be [B, 3, S, S] with S a multiple of 14")
+        _check_adapter_weights(ws, [(WIDTH, WIDTH)] * self.adapt_until + [(EMBED, WIDTH)] * (L + 1), self.device)
+        _check_image(x)
         if x.shape[0] > self.max_chunk(x.shape[-1]):
             raise ValueError(f"forward_train takes one chunk: at most {self.max_chunk(x.shape[-1])} images of "
                              f"{x.shape[-1]} px, got {x.shape[0]}")
@@ -226,8 +339,7 @@ class VisualEngine:
 
     @_on_device
     def _train_forward(self, x, ws, lowest):
-        """The launches of forward_raw() + forward() in fp32, with c_fc's pre-activation kept
-        (aaclip_gemm bias-only + aaclip_act: the epilogue's own device function) and every
+        """The launches of forward_raw() + forward() in fp32 (_train_block_fwd per block), every
         block above `lowest` writing fresh buffers. lowest = index of the lowest layer adapter
         that needs a gradient (None: only seg_proj / det_proj train, nothing of the tower is
         kept beyond the level taps)."""
@@ -236,9 +348,7 @@ class VisualEngine:
         g = S // PATCH
         P = g * g
         n_tok = P + 1
-        if self.pos.shape[0] != n_tok:
-            raise ValueError(f"positional embedding has {self.pos.shape[0]} rows, image needs {n_tok} "
-                             "(resize it at load time, reference model/model.py:395-426)")
+        _check_pos(self.pos, n_tok)
         R, W, dev = B * n_tok, WIDTH, self.device
         e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
         cols, X, H = e(B * P, KPATCH), e(R, W), e(R, W)
@@ -247,45 +357,21 @@ class VisualEngine:
         ops.embed_ln(X, self.cls, self.pos, self.ln_pre, self.blocks[0]["ln1"], H, B, n_tok)
         lvl = {lv: j for j, lv in enumerate(self.levels)}
         last, L, au = self.levels[-1], len(self.levels), self.adapt_until
-        qkv, att, fc, u = e(R, 3 * W), e(R, W), e(R, 4 * W), e(R, W)
-        fc_pre = fc
+        scratch = (e(R, 3 * W), e(R, W), e(R, 4 * W), e(R, W))  # qkv, att, fc, u of the blocks without a backward
         taps = [e(B * P, W) for _ in range(L)]
         saved, x_tap = {}, {}
+        attend = lambda qkv, att: ops.attention(qkv, att, B, n_tok, HEADS)  # noqa: E731
         for i in range(last):
-            blk = self.blocks[i]
             keep = lowest is not None and i > lowest        # this block has a backward
             adapt = i < au
             keep_blend = lowest is not None and adapt and i >= lowest
-            if keep:
-                qkv, att, fc_pre = e(R, 3 * W), e(R, W), e(R, 4 * W)
-            ops.gemm(H, blk["w_qkv"], qkv, bias=blk["b_qkv"])
-            ops.attention(qkv, att, B, n_tok, HEADS)
-            x_in = X
-            x_mid = e(R, W) if keep else X
-            ops.gemm(att, blk["w_o"], x_mid, bias=blk["b_o"], residual=x_in)
-            ops.layernorm(x_mid, blk["ln2"][0], blk["ln2"][1], H)
-            if keep:
-                ops.gemm(H, blk["w_fc"], fc_pre, bias=blk["b_fc"])
-                ops.act(fc_pre, self.act, out=fc)
-            else:
-                ops.gemm(H, blk["w_fc"], fc, bias=blk["b_fc"], gelu=self.act)
-            X = e(R, W) if (keep or keep_blend) else x_mid
-            ops.gemm(fc, blk["w_pr"], X, bias=blk["b_pr"], residual=x_mid)
-            if keep:
-                saved[i] = dict(x_in=x_in, qkv=qkv, att=att, x_mid=x_mid, fc_pre=fc_pre)
+            # attention_bwd_tiled reads the forward's output: att is kept
+            X, u = _train_block_fwd(self.blocks[i], X, H, scratch, attend, keep=keep, keep_blend=keep_blend,
+                                    keep_att=True, act=self.act, w_adapt=ws[i] if adapt else None, saved=saved, i=i)
             tap = taps[lvl[i + 1]] if (i + 1) in lvl else None
             nxt = self.blocks[i + 1]["ln1"] if i + 1 < last else None
-            uu = None
-            if adapt:
-                if keep_blend:
-                    u = e(R, W)
-                ops.gemm(X, ws[i], u, leaky=True)
-                if keep_blend:  # the blend is in place: keep the pre-blend x, blend a copy
-                    saved.setdefault(i, {}).update(x_pre=X, u=u)
-                    X = X.clone()
-                uu = u
-            if uu is not None or nxt is not None or tap is not None:
-                ops.block_tail(X, n_tok, u=uu, adapt_weight=self.i_w, ln=nxt, h=H if nxt else None,
+            if u is not None or nxt is not None or tap is not None:
+                ops.block_tail(X, n_tok, u=u, adapt_weight=self.i_w, ln=nxt, h=H if nxt else None,
                                post=self.ln_post, tap=tap)
             if tap is not None and lowest is not None and i >= lowest:
                 x_tap[lvl[i + 1]] = X  # the stream the tap read: the blocks above write fresh buffers
@@ -337,11 +423,14 @@ class VisualEngine:
                     ops.gemm(d, wt(ws[au + j]), dtaps[lv], residual=dtaps[lv])
         if lowest is None:
             return grads
-        bw = self._bwd_weights()
+        if self._bwd is None:
+            self._bwd = _bwd_weights(self.blocks, last)
         lvl = {lv: j for j, lv in enumerate(self.levels)}
         g = torch.zeros(R, W, device=dev, dtype=torch.float32)
         d_qkv, d_wide, d_w, du = e(R, 3 * W), e(R, 4 * W), e(R, W), e(R, W)
         attn_ws = ops.attention_bwd_tiled_workspace(B, n_tok, HEADS, dev)
+        attend_bwd = lambda sv, d_att, dqkv: ops.attention_bwd_tiled(  # noqa: E731
+            sv["qkv"], sv["att"], d_att, B, n_tok, HEADS, dqkv=dqkv, workspace=attn_ws)
         act_mode = "quick" if self.act == "quick" else "gelu"
         taps = {}
         for i in range(last - 1, lowest - 1, -1):
@@ -349,26 +438,10 @@ class VisualEngine:
             if j is not None and dtaps[j] is not None:  # the level tap read x after block i (blend included)
                 ops.tap_ln_bwd(dtaps[j], st["x_tap"][j], self.ln_post[0], g, B, n_tok)
             sv = st["blocks"].get(i, {})
-            if "u" in sv:  # x <- w u |x| / |u| + (1 - w) x after block i, u = LeakyReLU(x Wa_i^T)
-                ops.adapter_blend_bwd(g, sv["x_pre"], sv["u"], self.i_w, dx=g, du=du)
-                ops.act_bwd(du, sv["u"], "leaky", out=du)
-                if need[i]:
-                    grads[i] = ops.linear_wgrad(du, sv["x_pre"])
-                if i > lowest:
-                    ops.gemm(du, wt(ws[i]), g, residual=g)
-            if i in self.tap_blocks:  # diagnostic: dL/d(block i's own output), the adapter path included
-                taps[i] = g.clone() if i > lowest else ops.gemm(du, wt(ws[i]), e(R, W), residual=g)
+            _blend_bwd(i, lowest, g, du, sv, ws, self.i_w, need, grads, taps if i in self.tap_blocks else None)
             if i == lowest:
                 break
-            blk, bt = self.blocks[i], bw[i]
-            ops.gemm(g, bt["w_pr"], d_wide)                                    # 1. d_act = g . W_pr
-            ops.act_bwd(d_wide, sv["fc_pre"], act_mode, out=d_wide)            # 2. d_pre = d_act gelu'(fc_pre)
-            ops.gemm(d_wide, bt["w_fc"], d_w)                                  # 3. d_h2 = d_pre . W_fc
-            ops.layernorm_bwd(d_w, sv["x_mid"], blk["ln2"][0], residual=g, out=g)  # 4. g_mid
-            ops.gemm(g, bt["w_o"], d_w)                                        # 5. d_att = g_mid . W_o
-            ops.attention_bwd_tiled(sv["qkv"], sv["att"], d_w, B, n_tok, HEADS, dqkv=d_qkv, workspace=attn_ws)  # 6.
-            ops.gemm(d_qkv, bt["w_qkv"], d_w)                                  # 7. d_h1 = d_qkv . W_qkv
-            ops.layernorm_bwd(d_w, sv["x_in"], blk["ln1"][0], residual=g, out=g)   # 8. g_in
+            _block_bwd(g, self.blocks[i], self._bwd[i], sv, attend_bwd, act_mode, d_qkv, d_wide, d_w)
         if self.tap_blocks:
             self.tap_records.append(dict(B=B, n_tok=n_tok, taps=taps))
         return grads
@@ -382,9 +455,7 @@ class VisualEngine:
         g = S // PATCH
         P = g * g
         n_tok = P + 1
-        if self.pos.shape[0] != n_tok:
-            raise ValueError(f"positional embedding has {self.pos.shape[0]} rows, image needs {n_tok} "
-                             "(resize it at load time, reference model/model.py:395-426)")
+        _check_pos(self.pos, n_tok)
         R = B * n_tok
         dev, cdt = self.device, self.dtype
         e = lambda *s, dt=cdt: torch.empty(*s, device=dev, dtype=dt)  # noqa: E731
@@ -471,8 +542,7 @@ class VisualEngine:
         det_raw [B*P, 768] view, workspace). Rows are unnormalised projections.
         With T (predict, 16-bit modes) the projections are written as anomaly-map
         partials against T into ws["spart"] instead, and (None, None, ws) is returned."""
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[2] % PATCH:
-            raise ValueError("input must be [B, 3, S, S] with S a multiple of 14")
+        _check_image(x)
         x = x.to(self.device, torch.float32).contiguous()
         B, _, S, _ = x.shape
         ws = self._workspace(B, S, slot)
@@ -482,10 +552,22 @@ class VisualEngine:
         ops.gemm(ws["cols"], self.conv, X, row_group=P, row_group_out=n_tok, row_offset=1)
         lvl = {lv: j for j, lv in enumerate(self.levels)}
         last = self.levels[-1]
+        a8, asc, f8, fsc = ws["a8"], ws["asc"], ws["f8"], ws["fsc"]  # None outside the fp8 modes
+
+        def mlp_fp8(blk, aux):  # both fp8 scopes: ln_2 -> MX e4m3 -> c_fc (fp8, GELU, MX out) -> c_proj (fp8)
+            ops.layernorm(X, blk["ln2"][0], blk["ln2"][1], a8, y_sc=asc)
+            ops.gemm_fp8mx(a8, asc, blk["w_fc"][0], blk["w_fc"][1], f8, out_sc=fsc, bias=blk["b_fc"], gelu=self.act)
+            ops.gemm_fp8mx(f8, fsc, blk["w_pr"][0], blk["w_pr"][1], X, bias=blk["b_pr"], residual=X, aux=aux)
+
+        def mlp_16(blk, aux):  # 16-bit and fp32 modes
+            ops.layernorm(X, blk["ln2"][0], blk["ln2"][1], H)
+            ops.gemm(H, blk["w_fc"], ws["fc"], bias=blk["b_fc"], gelu=self.act)
+            ops.gemm(ws["fc"], blk["w_pr"], X, bias=blk["b_pr"], residual=X, aux=aux)
+
+        mlp = mlp_fp8 if self.fp8 else mlp_16
         if self.fp8 and not self.fp8_mlp_only:
             # every GEMM input is MX e4m3, written directly by its producer: the LayerNorm
             # kernels, the attention epilogue and the c_fc epilogue (no quantisation pass)
-            a8, asc, f8, fsc = ws["a8"], ws["asc"], ws["f8"], ws["fsc"]
             Hq, Hsc = a8, asc
             ops.embed_ln(X, self.cls, self.pos, self.ln_pre, self.blocks[0]["ln1"], a8, B, n_tok, h_sc=asc)
 
@@ -497,11 +579,6 @@ class VisualEngine:
 
             def out_proj(blk):
                 ops.gemm_fp8mx(a8, asc, blk["w_o"][0], blk["w_o"][1], X, bias=blk["b_o"], residual=X)
-
-            def mlp(blk, aux):  # c_fc writes e4m3 + block scales that c_proj consumes directly
-                ops.layernorm(X, blk["ln2"][0], blk["ln2"][1], a8, y_sc=asc)
-                ops.gemm_fp8mx(a8, asc, blk["w_fc"][0], blk["w_fc"][1], f8, out_sc=fsc, bias=blk["b_fc"], gelu=self.act)
-                ops.gemm_fp8mx(f8, fsc, blk["w_pr"][0], blk["w_pr"][1], X, bias=blk["b_pr"], residual=X, aux=aux)
         else:
             Hq, Hsc = H, None
             ops.embed_ln(X, self.cls, self.pos, self.ln_pre, self.blocks[0]["ln1"], H, B, n_tok)
@@ -514,22 +591,6 @@ class VisualEngine:
 
             def out_proj(blk):
                 ops.gemm(ws["attn"], blk["w_o"], X, bias=blk["b_o"], residual=X)
-
-            def ln2(blk, y, y_sc=None):
-                ops.layernorm(X, blk["ln2"][0], blk["ln2"][1], y, y_sc=y_sc)
-
-            def mlp(blk, aux):
-                if self.fp8_mlp_only:  # ln_2 -> MX e4m3 -> c_fc (fp8, GELU, MX out) -> c_proj (fp8)
-                    a8, asc, f8, fsc = ws["a8"], ws["asc"], ws["f8"], ws["fsc"]
-                    ln2(blk, a8, y_sc=asc)
-                    ops.gemm_fp8mx(a8, asc, blk["w_fc"][0], blk["w_fc"][1], f8, out_sc=fsc, bias=blk["b_fc"],
-                                   gelu=self.act)
-                    ops.gemm_fp8mx(f8, fsc, blk["w_pr"][0], blk["w_pr"][1], X, bias=blk["b_pr"], residual=X,
-                                   aux=aux)
-                    return
-                ln2(blk, H)
-                ops.gemm(H, blk["w_fc"], ws["fc"], bias=blk["b_fc"], gelu=self.act)
-                ops.gemm(ws["fc"], blk["w_pr"], X, bias=blk["b_pr"], residual=X, aux=aux)
         for i in range(last):
             blk = self.blocks[i]
             qkv(blk)
@@ -772,9 +833,8 @@ class _VisualTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, engine, x, *ws):
-        need = ctx.needs_input_grad[2:]
-        low = [i for i in range(engine.adapt_until) if need[i]]
-        out, det, st = engine._train_forward(x, [w.detach() for w in ws], low[0] if low else None)
+        lowest = _lowest_trainable(ctx.needs_input_grad[2:], engine.adapt_until)
+        out, det, st = engine._train_forward(x, [w.detach() for w in ws], lowest)
         ctx.engine, ctx.st = engine, st
         ctx.save_for_backward(*ws)
         return (*out, det)
@@ -812,14 +872,8 @@ class TextEngine:
         self.blocks = []
         for i in range(nl):
             p = f"transformer.resblocks.{i}."
-            self.blocks.append(dict(
-                ln1=(f32(params[p + "ln_1.weight"]), f32(params[p + "ln_1.bias"])),
-                ln2=(f32(params[p + "ln_2.weight"]), f32(params[p + "ln_2.bias"])),
-                w_qkv=cdt(params[p + "attn.in_proj_weight"]), b_qkv=f32(params[p + "attn.in_proj_bias"]),
-                w_o=cdt(params[p + "attn.out_proj.weight"]), b_o=f32(params[p + "attn.out_proj.bias"]),
-                w_fc=cdt(params[p + "mlp.c_fc.weight"]), b_fc=f32(params[p + "mlp.c_fc.bias"]),
-                w_pr=cdt(params[p + "mlp.c_proj.weight"]), b_pr=f32(params[p + "mlp.c_proj.bias"]),
-            ))
+            self.blocks.append(_pack_block(params, p, dev, dtype, w_qkv=cdt(params[p + "attn.in_proj_weight"]),
+                                           b_qkv=f32(params[p + "attn.in_proj_bias"])))
         self.adapted = text_adapter is not None
         self.t_w = float(text_adapt_weight)
         self._bwd = None  # transposed frozen weights for the input-gradient GEMMs (encode_train)
@@ -897,16 +951,6 @@ class TextEngine:
         return T
 
     # ------------------------------------------------------------------ training (stage 1)
-    def _bwd_weights(self):
-        """W^T copies of the frozen block weights: dX = dY . W is aaclip_gemm (C = A . W'^T)
-        with W' = W^T. Packed once per engine, on the first training call; block 0 never
-        needs a backward (no trainable weight lies below the adapter that follows it)."""
-        if self._bwd is None:
-            tr = lambda w: w.t().contiguous()  # noqa: E731
-            self._bwd = [None] + [dict(w_qkv=tr(b["w_qkv"]), w_o=tr(b["w_o"]), w_fc=tr(b["w_fc"]), w_pr=tr(b["w_pr"]))
-                                  for b in self.blocks[1:]]
-        return self._bwd
-
     def encode_train(self, tokens: torch.Tensor, adapter_weights, truncate: bool = True) -> torch.Tensor:
         """encode() with a grad_fn into the text adapter: adapter_weights are the adapt_until
         SimpleAdapter weights followed by the output SimpleProj weight ([width, width] ...,
@@ -919,22 +963,16 @@ class TextEngine:
         if self.dtype != torch.float32:
             raise RuntimeError("the text tower trains in fp32 only")
         ws = list(adapter_weights)
-        if len(ws) != self.adapt_until + 1:
-            raise ValueError(f"expected {self.adapt_until + 1} adapter weights, got {len(ws)}")
         W = self.width
-        for i, w in enumerate(ws):
-            want = (W, W) if i < self.adapt_until else (self.w_out.shape[0], W)
-            if w.device != self.device or w.dtype != torch.float32 or tuple(w.shape) != want or not w.is_contiguous():
-                raise ValueError(f"adapter weight {i} must be a contiguous fp32 {list(want)} tensor on {self.device}")
+        _check_adapter_weights(ws, [(W, W)] * self.adapt_until + [(self.w_out.shape[0], W)], self.device)
         if tokens.dim() != 2 or tokens.shape[1] != self.pos.shape[0]:
             raise ValueError("token context length mismatch")
         return _TextTrain.apply(self, tokens, bool(truncate), *ws)
 
     @_on_device
     def _train_forward(self, tokens, truncate, ws, lowest):
-        """The launches of encode(), with c_fc's pre-activation kept (aaclip_gemm bias-only +
-        aaclip_act: the epilogue's own device function) and every block from `lowest` + 1 up
-        writing fresh buffers. lowest = index of the lowest adapter that needs a gradient
+        """The launches of encode() (_train_block_fwd per block), every block from `lowest` + 1
+        up writing fresh buffers. lowest = index of the lowest adapter that needs a gradient
         (None: only the output projection trains, nothing below the EOT rows is kept)."""
         n, ctx = tokens.shape
         if truncate and n > 0:
@@ -945,40 +983,20 @@ class TextEngine:
         dev = self.device
         e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
         X, H = e(R, W), e(R, W)
-        qkv, att, fc = e(R, 3 * W), e(R, W), e(R, 4 * W)
-        fc_pre, u = fc, e(R, W)
+        scratch = (e(R, 3 * W), e(R, W), e(R, 4 * W), e(R, W))  # qkv, att, fc, u of the blocks without a backward
         ops.text_embed_ln(tokens, self.tok_emb, self.pos, self.blocks[0]["ln1"], X, H)
         nb = len(self.blocks)
         saved = {}
+        attend = lambda qkv, att: ops.attention(qkv, att, n, ctx, self.heads, causal=True)  # noqa: E731
         for i, blk in enumerate(self.blocks):
             keep = lowest is not None and i > lowest        # this block has a backward
             adapt = i < self.adapt_until
             keep_blend = lowest is not None and adapt and i >= lowest
-            if keep:
-                qkv, fc_pre = e(R, 3 * W), e(R, 4 * W)
-            ops.gemm(H, blk["w_qkv"], qkv, bias=blk["b_qkv"])
-            ops.attention(qkv, att, n, ctx, self.heads, causal=True)
-            x_in = X
-            x_mid = e(R, W) if keep else X
-            ops.gemm(att, blk["w_o"], x_mid, bias=blk["b_o"], residual=x_in)
-            ops.layernorm(x_mid, blk["ln2"][0], blk["ln2"][1], H)
-            if keep:
-                ops.gemm(H, blk["w_fc"], fc_pre, bias=blk["b_fc"])
-                ops.act(fc_pre, self.act, out=fc)
-            else:
-                ops.gemm(H, blk["w_fc"], fc, bias=blk["b_fc"], gelu=self.act)
-            X = e(R, W) if (keep or keep_blend) else x_mid
-            ops.gemm(fc, blk["w_pr"], X, bias=blk["b_pr"], residual=x_mid)
-            if keep:
-                saved[i] = dict(x_in=x_in, qkv=qkv, x_mid=x_mid, fc_pre=fc_pre)
+            # attention_bwd takes qkv and dout only: att is not kept
+            X, u = _train_block_fwd(blk, X, H, scratch, attend, keep=keep, keep_blend=keep_blend, keep_att=False,
+                                    act=self.act, w_adapt=ws[i] if adapt else None, saved=saved, i=i)
             nxt = self.blocks[i + 1]["ln1"] if i + 1 < nb else None
             if adapt:
-                if keep_blend:
-                    u = e(R, W)
-                ops.gemm(X, ws[i], u, leaky=True)
-                if keep_blend:  # the blend is in place: keep the pre-blend x, blend a copy
-                    saved.setdefault(i, {}).update(x_pre=X, u=u)
-                    X = X.clone()
                 ops.block_tail(X, ctx, u=u, adapt_weight=self.t_w, ln=nxt, h=H if nxt else None)
             elif nxt is not None:
                 ops.layernorm(X, nxt[0], nxt[1], H)
@@ -1003,35 +1021,21 @@ class TextEngine:
             grads[-1] = ops.linear_wgrad(d_o, st["eot"])
         if lowest is None:
             return grads
-        bw = self._bwd_weights()
+        if self._bwd is None:
+            self._bwd = _bwd_weights(self.blocks, len(self.blocks))
         d_eot = ops.gemm(d_o, ws[-1].detach().t().contiguous(), e(n, W))
         g = ops.eot_ln_bwd(d_eot, st["x_final"], tokens, self.ln_final[0])
         d_qkv, d_wide, d_w, du = e(R, 3 * W), e(R, 4 * W), e(R, W), e(R, W)
+        attend_bwd = lambda sv, d_att, dqkv: ops.attention_bwd(  # noqa: E731
+            sv["qkv"], d_att, n, ctx, self.heads, causal=True, dqkv=dqkv)
         act_mode = "quick" if self.act == "quick" else "gelu"
         taps = {}
         for i in range(len(self.blocks) - 1, lowest - 1, -1):
             sv = st["blocks"].get(i, {})
-            if "u" in sv:  # x <- w u |x| / |u| + (1 - w) x after block i, u = LeakyReLU(x Wa_i^T)
-                ops.adapter_blend_bwd(g, sv["x_pre"], sv["u"], self.t_w, dx=g, du=du)
-                ops.act_bwd(du, sv["u"], "leaky", out=du)
-                if need[i]:
-                    grads[i] = ops.linear_wgrad(du, sv["x_pre"])
-                if i > lowest:
-                    ops.gemm(du, ws[i].detach().t().contiguous(), g, residual=g)
-            if i in self.tap_blocks:  # diagnostic: dL/d(block i's own output), the adapter path included
-                taps[i] = g.clone() if i > lowest else ops.gemm(du, ws[i].detach().t().contiguous(), e(R, W),
-                                                                residual=g)
+            _blend_bwd(i, lowest, g, du, sv, ws, self.t_w, need, grads, taps if i in self.tap_blocks else None)
             if i == lowest:
                 break
-            blk, bt = self.blocks[i], bw[i]
-            ops.gemm(g, bt["w_pr"], d_wide)                                    # 1. d_act = g . W_pr
-            ops.act_bwd(d_wide, sv["fc_pre"], act_mode, out=d_wide)            # 2. d_pre = d_act gelu'(fc_pre)
-            ops.gemm(d_wide, bt["w_fc"], d_w)                                  # 3. d_h2 = d_pre . W_fc
-            ops.layernorm_bwd(d_w, sv["x_mid"], blk["ln2"][0], residual=g, out=g)  # 4. g_mid
-            ops.gemm(g, bt["w_o"], d_w)                                        # 5. d_att = g_mid . W_o
-            ops.attention_bwd(sv["qkv"], d_w, n, ctx, self.heads, causal=True, dqkv=d_qkv)  # 6.
-            ops.gemm(d_qkv, bt["w_qkv"], d_w)                                  # 7. d_h1 = d_qkv . W_qkv
-            ops.layernorm_bwd(d_w, sv["x_in"], blk["ln1"][0], residual=g, out=g)   # 8. g_in
+            _block_bwd(g, self.blocks[i], self._bwd[i], sv, attend_bwd, act_mode, d_qkv, d_wide, d_w)
         if self.tap_blocks:
             self.tap_records.append(dict(n=n, ctx=ctx, taps=taps))
         return grads
@@ -1042,10 +1046,8 @@ class _TextTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, engine, tokens, truncate, *ws):
-        need = ctx.needs_input_grad[3:]
-        low = [i for i in range(engine.adapt_until) if need[i]]
-        dws = [w.detach() for w in ws]
-        out, st = engine._train_forward(tokens, truncate, dws, low[0] if low else None)
+        lowest = _lowest_trainable(ctx.needs_input_grad[3:], engine.adapt_until)
+        out, st = engine._train_forward(tokens, truncate, [w.detach() for w in ws], lowest)
         ctx.engine, ctx.st = engine, st
         ctx.save_for_backward(*ws, out)  # the output (LeakyReLU's backward reads it) goes through autograd
         return out
@@ -1089,17 +1091,8 @@ class FrozenVisualEngine:
         if dev.type != "cuda":
             raise RuntimeError("FrozenVisualEngine needs device tensors (no CPU path)")
         self.device = dev
-        f32 = lambda t: t.detach().to(dev, torch.float32).contiguous()  # noqa: E731
-        cdt = lambda t: t.detach().to(dev, dtype).contiguous()  # noqa: E731
-        w = vparams["visual.conv1.weight"].detach().reshape(WIDTH, -1)
-        conv = torch.zeros(WIDTH, KPATCH, device=dev, dtype=torch.float32)
-        conv[:, : w.shape[1]] = w
-        self.conv = conv.to(dtype).contiguous()
-        self.cls = f32(vparams["visual.class_embedding"])
-        self.pos = f32(vparams["visual.positional_embedding"])
-        self.ln_pre = (f32(vparams["visual.ln_pre.weight"]), f32(vparams["visual.ln_pre.bias"]))
-        self.ln_post = (f32(vparams["visual.ln_post.weight"]), f32(vparams["visual.ln_post.bias"]))
-        self.w_proj = cdt(vparams["visual.proj"].detach().t())  # x @ proj == x . (proj^T)^T
+        self.conv, self.cls, self.pos, self.ln_pre, self.ln_post = _pack_visual_stem(vparams, dev, dtype)
+        self.w_proj = _to(vparams["visual.proj"].t(), dev, dtype)  # x @ proj == x . (proj^T)^T
         self.q_prescaled = dtype != torch.float32  # log2(e)/8 folded into the Q rows (as VisualEngine)
         self.blocks = []
         for i in range(LAYERS):
@@ -1112,14 +1105,7 @@ class FrozenVisualEngine:
                 w_in, b_in = w_in.clone(), b_in.clone()
                 w_in[:WIDTH] *= Q_LOG2_SCALE
                 b_in[:WIDTH] *= Q_LOG2_SCALE
-            self.blocks.append(dict(
-                ln1=(f32(vparams[p + "ln_1.weight"]), f32(vparams[p + "ln_1.bias"])),
-                ln2=(f32(vparams[p + "ln_2.weight"]), f32(vparams[p + "ln_2.bias"])),
-                w_in=cdt(w_in), b_in=b_in.contiguous(),
-                w_o=cdt(vparams[p + "attn.out_proj.weight"]), b_o=f32(vparams[p + "attn.out_proj.bias"]),
-                w_fc=cdt(vparams[p + "mlp.c_fc.weight"]), b_fc=f32(vparams[p + "mlp.c_fc.bias"]),
-                w_pr=cdt(vparams[p + "mlp.c_proj.weight"]), b_pr=f32(vparams[p + "mlp.c_proj.bias"]),
-            ))
+            self.blocks.append(_pack_block(vparams, p, dev, dtype, w_in=_to(w_in, dev, dtype), b_in=b_in.contiguous()))
         self._ws = {}
         self._patch = None
         self.poison = False  # tests: fill new workspaces with NaN (read-before-write screen)
@@ -1137,9 +1123,7 @@ class FrozenVisualEngine:
         g = S // PATCH
         P = g * g
         n_tok = P + 1
-        if self.pos.shape[0] != n_tok:
-            raise ValueError(f"positional embedding has {self.pos.shape[0]} rows, image needs {n_tok} "
-                             "(resize it at load time, reference model/model.py:395-426)")
+        _check_pos(self.pos, n_tok)
         R = B * n_tok
         dev, cdt = self.device, self.dtype
         e = lambda *s, dt=cdt: torch.empty(*s, device=dev, dtype=dt)  # noqa: E731
@@ -1210,8 +1194,7 @@ class FrozenVisualEngine:
         [B, n_tok, 1024] fp32 tensor for each i in 1..24 that is in out_layers, ascending]).
         All 24 blocks always run. patch_features=True also keeps ln_post(patch rows after
         block 24) @ proj for patch_features() (AdaptedCLIP.forward_original)."""
-        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[2] % PATCH:
-            raise ValueError("input must be [B, 3, S, S] with S a multiple of 14")
+        _check_image(x)
         out_layers = set(int(i) for i in out_layers)
         x = x.to(self.device, torch.float32).contiguous()
         B, S = x.shape[0], x.shape[-1]
