@@ -406,11 +406,42 @@ def _mx_out(t, sc, rows):
     return (dtag(t) if t is not None else None), None, 0
 
 
+def _rows32(t, name, shape=None):
+    """A contiguous fp32 [rows, width] operand: the fused row kernels stride by the width alone."""
+    if t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous() \
+            or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{name} must be contiguous fp32 [rows, width]" + (f" {list(shape)}" if shape is not None else ""))
+
+
+def _rows_out(t, name, shape):
+    """A contiguous [rows, width] output (its dtype is checked by dtag / _mx_out)."""
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous {list(shape)}")
+
+
+def _ln_pair(ln, name, width):
+    if len(ln) != 2:
+        raise ValueError(f"{name} must be a (weight, bias) pair")
+    _f32c(ln[0], name + " weight", (width,))
+    _f32c(ln[1], name + " bias", (width,))
+
+
+def _tokens32(tokens):
+    if tokens.dim() != 2 or tokens.dtype != torch.int32 or not tokens.is_contiguous():
+        raise ValueError("tokens must be contiguous int32 [n_seq, ctx]")
+
+
 def embed_ln(x, cls, pos, ln_pre, ln1, h, batch, n_tok, h_sc=None):
-    _dev(x, h)
+    _dev(x, h, cls, pos, *ln_pre, *ln1)
+    _rows32(x, "x")
     width = x.shape[1]
     if x.shape[0] != batch * n_tok or h.shape != x.shape or pos.shape != (n_tok, width):
         raise ValueError("embed_ln shape mismatch")
+    _rows_out(h, "h", x.shape)
+    _f32c(cls, "cls", (width,))
+    _rows32(pos, "pos")
+    _ln_pair(ln_pre, "ln_pre", width)
+    _ln_pair(ln1, "ln1", width)
     od, scp, ld = _mx_out(h, h_sc, x.shape[0])
     _launch("embed_ln", "embed_ln_kernel", 0.0, x.numel() * 4 * 2 + h.numel() * h.element_size(), "aaclip_embed_ln",
             od, _ptr(x), _ptr(cls), _ptr(pos), _ptr(ln_pre[0]), _ptr(ln_pre[1]), _ptr(ln1[0]), _ptr(ln1[1]),
@@ -419,14 +450,23 @@ def embed_ln(x, cls, pos, ln_pre, ln1, h, batch, n_tok, h_sc=None):
 
 def block_tail(x, n_tok, *, u=None, adapt_weight=0.0, ln=None, h=None, post=None, tap=None, out_dtype=None,
                h_sc=None):
-    _dev(x, u, h, tap)
+    _dev(x, u, h, tap, *(ln or ()), *(post or ()))
+    _rows32(x, "x")
     rows, width = x.shape
-    if u is not None and u.shape != x.shape:
-        raise ValueError("adapter output shape mismatch")
-    if h is not None and h.shape != x.shape:
-        raise ValueError("h shape mismatch")
-    if tap is not None and tap.shape != (rows // n_tok * (n_tok - 1), width):
-        raise ValueError("tap shape mismatch")
+    if u is not None:
+        _rows32(u, "adapter output u", x.shape)
+    if h is not None:
+        _rows_out(h, "h", x.shape)
+        if not ln:
+            raise ValueError("h needs the (weight, bias) pair ln")
+    if tap is not None:
+        if n_tok < 2 or rows % n_tok or not post:
+            raise ValueError("a tap needs post, n_tok > 1 and rows a multiple of n_tok")
+        _rows_out(tap, "tap", (rows // n_tok * (n_tok - 1), width))
+    if ln:
+        _ln_pair(ln, "ln", width)
+    if post:
+        _ln_pair(post, "post", width)
     od, scp, ld = _mx_out(h, h_sc, rows)
     if od is None:
         od = dtag(tap) if tap is not None else F32
@@ -441,11 +481,13 @@ def block_tail(x, n_tok, *, u=None, adapt_weight=0.0, ln=None, h=None, post=None
 
 
 def layernorm(x, w, b, y, y_sc=None):
-    _dev(x, y)
+    _dev(x, y, w, b)
     _rowmajor(x, "x")
     _rowmajor(y, "y")
     if x.shape != y.shape or x.dtype != torch.float32:
         raise ValueError("layernorm shape/dtype mismatch")
+    _f32c(w, "layernorm weight", (x.shape[1],))
+    _f32c(b, "layernorm bias", (x.shape[1],))
     od, scp, ld = _mx_out(y, y_sc, x.shape[0])
     _launch("layernorm", "layernorm_kernel", 0.0, x.numel() * 4 + y.numel() * y.element_size(), "aaclip_layernorm",
             od, _ptr(x), x.stride(0), _ptr(w), _ptr(b), _ptr(y), y.stride(0), x.shape[0], x.shape[1], scp, ld,
@@ -454,19 +496,30 @@ def layernorm(x, w, b, y, y_sc=None):
 
 
 def text_embed_ln(tokens, tok_emb, pos, ln1, x, h):
-    _dev(tokens, x, h)
+    _dev(tokens, x, h, tok_emb, pos, *ln1)
+    _tokens32(tokens)
     n, ctx = tokens.shape
-    if tokens.dtype != torch.int32 or not tokens.is_contiguous() or x.shape != (n * ctx, tok_emb.shape[1]):
-        raise ValueError("text_embed_ln shape mismatch")
+    _rows32(tok_emb, "tok_emb")
+    width = tok_emb.shape[1]
+    _rows32(x, "x", (n * ctx, width))
+    _rows_out(h, "h", x.shape)
+    _rows32(pos, "pos")
+    if pos.shape[0] < ctx or pos.shape[1] != width:
+        raise ValueError("pos must be fp32 [>= ctx, width]")
+    _ln_pair(ln1, "ln1", width)
     call("aaclip_text_embed_ln", dtag(h), _ptr(tokens), _ptr(tok_emb), _ptr(pos), _ptr(ln1[0]), _ptr(ln1[1]),
          _ptr(x), _ptr(h), n, ctx, x.shape[1], _stream())
 
 
 def eot_ln(x, tokens, ln, y):
-    _dev(x, tokens, y)
+    _dev(x, tokens, y, *ln)
+    _tokens32(tokens)
     n, ctx = tokens.shape
-    if y.shape != (n, x.shape[1]) or x.shape[0] != n * ctx:
+    _rows32(x, "x")
+    if x.shape[0] != n * ctx:
         raise ValueError("eot_ln shape mismatch")
+    _rows_out(y, "y", (n, x.shape[1]))
+    _ln_pair(ln, "ln", x.shape[1])
     call("aaclip_eot_ln", dtag(y), _ptr(x), _ptr(tokens), _ptr(ln[0]), _ptr(ln[1]), _ptr(y), n, ctx,
          x.shape[1], _stream())
     return y
@@ -474,9 +527,14 @@ def eot_ln(x, tokens, ln, y):
 
 def anchor_reduce(emb: torch.Tensor, T: torch.Tensor, col: int):
     _dev(emb, T)
+    _rows32(emb, "emb")
     n, dim = emb.shape
-    if T.shape[0] != dim or emb.dtype != torch.float32 or not emb.is_contiguous():
-        raise ValueError("anchor_reduce shape mismatch")
+    if T.dim() != 2 or T.shape[0] != dim or T.dtype != torch.float32 or not T.is_contiguous():
+        raise ValueError("T must be contiguous fp32 [dim, ncols]")
+    if not 0 <= col < T.shape[1]:
+        raise ValueError(f"col {col} outside T's {T.shape[1]} columns")
+    if not (1 <= n <= 256 and dim <= 1024):
+        raise ValueError("anchor_reduce takes 1..256 rows of at most 1024 columns")
     call("aaclip_anchor_reduce", _ptr(emb), n, dim, _ptr(T), col, T.shape[1], _stream())
 
 
@@ -486,6 +544,8 @@ def l2_normalize(x, y):
     _rowmajor(y, "y")
     if x.shape != y.shape:
         raise ValueError("l2_normalize shape mismatch")
+    if x.stride(0) % 4 or y.stride(0) % 4:
+        raise ValueError("l2_normalize row strides must be multiples of 4 elements")
     call("aaclip_l2_normalize", dtag(x), dtag(y), _ptr(x), x.stride(0), _ptr(y), y.stride(0),
          x.shape[0], x.shape[1], _stream())
     return y
