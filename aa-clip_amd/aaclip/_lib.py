@@ -78,6 +78,11 @@ SIGNATURES = {
     "aaclip_linear_wgrad": [_P, _L, _P, _L, _I, _I, _I, _P, ctypes.c_size_t, _P, _L, _P],
     "aaclip_attention_bwd_tiled_workspace": [_I, _I, _I, ctypes.POINTER(ctypes.c_size_t)],
     "aaclip_attention_bwd_tiled": [_P, _P, _P, _P, _I, _I, _I, _I, _P, ctypes.c_size_t, _P],
+    "aaclip_attention_bwd16_workspace": [_I, _I, _I, ctypes.POINTER(ctypes.c_size_t)],
+    "aaclip_attention_bwd16": [_I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, ctypes.c_size_t, _P],
+    "aaclip_act_to16": [_I, _P, _P, _I, _L, _P],
+    "aaclip_act_bwd16": [_I, _P, _P, _P, _I, _L, _P],
+    "aaclip_cast_rows": [_I, _I, _P, _L, _P, _L, _I, _I, _P],
     "aaclip_tap_ln_bwd": [_P, _P, _P, _P, _I, _I, _I, _P],
     "aaclip_l2_normalize_bwd": [_P, _L, _I, _F, _P, _L, _P, _L, _I, _I, _P],
     "aaclip_anomaly_map": [_I, _P, _I, _L, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P],

@@ -6,7 +6,8 @@ AdaptedCLIP.encode_text / CLIP.encode_text (adapter.py:114-145,
 model/model.py:190-201) + the prompt-ensemble anchors (forward_utils.py:138-162), and
 TextEngine.encode_train, the same forward with a HIP backward into the text adapter
 weights (stage 1, train.py:38-114); VisualEngine.forward_train, forward() with a HIP
-backward into the image adapter weights (stage 2, train.py:117-174).
+backward into the image adapter weights (stage 2, train.py:117-174), in fp32 or, on a bf16 engine,
+in bf16 mixed precision (fp32 residual / gradient streams and weights, bf16 GEMM inputs).
 
 Data layout in HBM (token-major "NLD", one row per token):
   x      fp32 [B*(P+1), 1024]   residual stream (kept fp32 across all 24 blocks)
@@ -137,32 +138,41 @@ def _lowest_trainable(need, adapt_until: int):
 
 
 def _bwd_weights(blocks: list, upto: int):
-    """W^T copies of the frozen weights of blocks 1..upto-1: dX = dY . W is aaclip_gemm
-    (C = A . W'^T) with W' = W^T. Packed once per engine, on the first training call; block 0
-    never needs a backward (no trainable weight lies below the adapter that follows it)."""
+    """W^T copies of the frozen weights of blocks 1..upto-1, in the dtype they are packed in: dX =
+    dY . W is aaclip_gemm (C = A . W'^T) with W' = W^T. Packed once per engine, on the first
+    training call; block 0 never needs a backward (no trainable weight lies below the adapter that
+    follows it). A bf16 engine's w_qkv carries the folded Q scale, so its transpose takes the
+    gradient of the prescaled q (aaclip_attention_bwd16 under AACLIP_ATTN_Q_PRESCALED)."""
     tr = lambda w: w.t().contiguous()  # noqa: E731
     return [None] + [dict(w_qkv=tr(b["w_qkv"]), w_o=tr(b["w_o"]), w_fc=tr(b["w_fc"]), w_pr=tr(b["w_pr"]))
                      for b in blocks[1:upto]]
 
 
 def _train_block_fwd(blk: dict, X, H, scratch, attend, *, keep: bool, keep_blend: bool, keep_att: bool, act,
-                     w_adapt, saved: dict, i: int):
-    """Block i of a training forward in fp32, from the QKV GEMM through c_proj and the adapter
+                     w_adapt, saved: dict, i: int, dtype=torch.float32):
+    """Block i of a training forward in `dtype`, from the QKV GEMM through c_proj and the adapter
     GEMM (w_adapt, or None): the inference block's launches. X: the residual stream, H: ln_1(X)
     on entry; scratch = (qkv, att, fc, u), what a block without a backward writes;
     attend(qkv, att) launches the tower's attention. keep: the block has a backward, so it
     writes fresh buffers, filed under saved[i], with c_fc's pre-activation kept (aaclip_gemm
     bias-only + aaclip_act: the epilogue's own device function); keep_att: att among them (the
     attention backward reads the forward's output). keep_blend: so has the adapter after it.
-    Returns (X, u) for the caller's block tail; u = LeakyReLU(adapter(X)), or None."""
+    Returns (X, u) for the caller's block tail; u = LeakyReLU(adapter(X)), or None.
+    dtype bfloat16 (mixed precision): X, u and the kept fc_pre stay fp32, H / qkv / att / fc are
+    bf16 and scratch carries a fifth buffer xb, the bf16 copy of X that c_proj's epilogue writes
+    for the adapter GEMM (the inference block's launches again); the kept pre-activation is
+    activated by aaclip_act_to16, the 16-bit epilogue's own function and rounding."""
     R, W = X.shape
     e = lambda *s: torch.empty(*s, device=X.device, dtype=torch.float32)  # noqa: E731
-    qkv, att, fc, u = scratch
+    c = lambda *s: torch.empty(*s, device=X.device, dtype=dtype)  # noqa: E731
+    low = dtype != torch.float32
+    qkv, att, fc, u = scratch[:4]
+    xb = scratch[4] if low and w_adapt is not None else None
     fc_pre = fc
     if keep:
-        qkv = e(R, 3 * W)
+        qkv = c(R, 3 * W)
         if keep_att:
-            att = e(R, W)
+            att = c(R, W)
         fc_pre = e(R, 4 * W)
     ops.gemm(H, blk["w_qkv"], qkv, bias=blk["b_qkv"])
     attend(qkv, att)
@@ -172,11 +182,14 @@ def _train_block_fwd(blk: dict, X, H, scratch, attend, *, keep: bool, keep_blend
     ops.layernorm(x_mid, blk["ln2"][0], blk["ln2"][1], H)
     if keep:
         ops.gemm(H, blk["w_fc"], fc_pre, bias=blk["b_fc"])
-        ops.act(fc_pre, act, out=fc)
+        if low:
+            ops.act_to16(fc_pre, act, out=fc)
+        else:
+            ops.act(fc_pre, act, out=fc)
     else:
         ops.gemm(H, blk["w_fc"], fc, bias=blk["b_fc"], gelu=act)
     X = e(R, W) if (keep or keep_blend) else x_mid
-    ops.gemm(fc, blk["w_pr"], X, bias=blk["b_pr"], residual=x_mid)
+    ops.gemm(fc, blk["w_pr"], X, bias=blk["b_pr"], residual=x_mid, aux=xb)
     if keep:
         saved[i] = dict(x_in=x_in, qkv=qkv, x_mid=x_mid, fc_pre=fc_pre)
         if keep_att:
@@ -185,41 +198,58 @@ def _train_block_fwd(blk: dict, X, H, scratch, attend, *, keep: bool, keep_blend
         return X, None
     if keep_blend:
         u = e(R, W)
-    ops.gemm(X, w_adapt, u, leaky=True)
+    ops.gemm(xb if low else X, w_adapt, u, leaky=True)
     if keep_blend:  # the blend is in place: keep the pre-blend x, blend a copy
         saved.setdefault(i, {}).update(x_pre=X, u=u)
         X = X.clone()
     return X, u
 
 
-def _blend_bwd(i: int, lowest: int, g, du, sv: dict, ws: list, adapt_weight: float, need, grads: list, taps):
+def _blend_bwd(i: int, lowest: int, g, du, sv: dict, ws: list, adapt_weight: float, need, grads: list, taps,
+               du16=None):
     """g = dL/d(x after block i, blended) -> dL/d(block i's own output), in place; sv: the
     block's saved dict (no "u": no trainable adapter follows it and g passes through). Fills
     grads[i] where need[i] asks; at block `lowest` the walk ends and the adapter path's dx is
-    not added. taps: the tap_blocks diagnostic's dict when it wants block i, else None."""
-    wt = lambda w: w.detach().t().contiguous()  # noqa: E731
+    not added. taps: the tap_blocks diagnostic's dict when it wants block i, else None.
+    du16 (mixed precision): the 16-bit buffer du is copied to for the input-gradient GEMM on
+    the adapter weight cast to its dtype; everything else here stays fp32."""
+    if du16 is None:
+        wt = lambda w: w.detach().t().contiguous()  # noqa: E731
+        lo = lambda t: t  # noqa: E731
+    else:
+        wt = lambda w: w.detach().to(du16.dtype).t().contiguous()  # noqa: E731
+        lo = lambda t: ops.cast_rows(t, du16)  # noqa: E731
     if "u" in sv:  # x <- w u |x| / |u| + (1 - w) x after block i, u = LeakyReLU(x Wa_i^T)
         ops.adapter_blend_bwd(g, sv["x_pre"], sv["u"], adapt_weight, dx=g, du=du)
         ops.act_bwd(du, sv["u"], "leaky", out=du)
         if need[i]:
             grads[i] = ops.linear_wgrad(du, sv["x_pre"])
         if i > lowest:
-            ops.gemm(du, wt(ws[i]), g, residual=g)
+            ops.gemm(lo(du), wt(ws[i]), g, residual=g)
     if taps is not None:  # diagnostic: dL/d(block i's own output), the adapter path included
-        taps[i] = g.clone() if i > lowest else ops.gemm(du, wt(ws[i]), torch.empty_like(g), residual=g)
+        taps[i] = g.clone() if i > lowest else ops.gemm(lo(du), wt(ws[i]), torch.empty_like(g), residual=g)
 
 
-def _block_bwd(g, blk: dict, bt: dict, sv: dict, attend_bwd, act_mode: str, d_qkv, d_wide, d_w):
+def _block_bwd(g, blk: dict, bt: dict, sv: dict, attend_bwd, act_mode: str, d_qkv, d_wide, d_w, lo=None):
     """g = dL/d(block output) -> dL/d(block input), in place, through the frozen block: the
     input-gradient GEMMs on the transposed weights bt (_bwd_weights), no weight gradient.
     attend_bwd(sv, d_att, d_qkv) launches the tower's attention backward; d_qkv / d_wide /
-    d_w are [R, 3W] / [R, 4W] / [R, W] scratch."""
-    ops.gemm(g, bt["w_pr"], d_wide)                                        # 1. d_act = g . W_pr
-    ops.act_bwd(d_wide, sv["fc_pre"], act_mode, out=d_wide)                # 2. d_pre = d_act gelu'(fc_pre)
+    d_w are [R, 3W] / [R, 4W] / [R, W] scratch.
+    lo = (g16, d_att16), [R, W] 16-bit scratch: mixed precision. g, d_w and both LayerNorm
+    backwards stay fp32; d_qkv / d_wide and bt are 16-bit, g is copied to g16 before steps 1 and 5
+    (aaclip_cast_rows), steps 1 and 5 write 16-bit, steps 3 and 7 write fp32 into d_w."""
+    if lo is None:
+        g16 = lambda: g  # noqa: E731
+        d_att, act_bwd = d_w, ops.act_bwd
+    else:
+        g16 = lambda: ops.cast_rows(g, lo[0])  # noqa: E731
+        d_att, act_bwd = lo[1], ops.act_bwd16
+    ops.gemm(g16(), bt["w_pr"], d_wide)                                    # 1. d_act = g . W_pr
+    act_bwd(d_wide, sv["fc_pre"], act_mode, out=d_wide)                    # 2. d_pre = d_act gelu'(fc_pre)
     ops.gemm(d_wide, bt["w_fc"], d_w)                                      # 3. d_h2 = d_pre . W_fc
     ops.layernorm_bwd(d_w, sv["x_mid"], blk["ln2"][0], residual=g, out=g)  # 4. g_mid
-    ops.gemm(g, bt["w_o"], d_w)                                            # 5. d_att = g_mid . W_o
-    attend_bwd(sv, d_w, d_qkv)                                             # 6. d_qkv
+    ops.gemm(g16(), bt["w_o"], d_att)                                      # 5. d_att = g_mid . W_o
+    attend_bwd(sv, d_att, d_qkv)                                           # 6. d_qkv
     ops.gemm(d_qkv, bt["w_qkv"], d_w)                                      # 7. d_h1 = d_qkv . W_qkv
     ops.layernorm_bwd(d_w, sv["x_in"], blk["ln1"][0], residual=g, out=g)   # 8. g_in
 
@@ -324,9 +354,12 @@ class VisualEngine:
         device, normally the live nn.Parameters), read as they are at the call. The outputs are
         bit-identical to forward()'s on the same weights; backward fills .grad of the weights
         that require it, walks the tower down to the lowest layer adapter that does and computes
-        nothing for the frozen weights. fp32 engines and a single chunk only."""
-        if self.dtype != torch.float32 or self.fp8:
-            raise RuntimeError("the visual tower trains in fp32 only")
+        nothing for the frozen weights. fp32 engines and, in mixed precision, bf16 engines (fp32
+        residual and gradient streams, adapter weights, .grads and LayerNorm / blend / normalise
+        backwards; bf16 GEMM inputs, the weights cast at each call); a single chunk only."""
+        if self.dtype not in (torch.float32, torch.bfloat16) or self.fp8:
+            raise RuntimeError("the visual tower trains in fp32 only, or in bf16 mixed precision (fp16 and "
+                               "fp8 engines do not train: fp16 would need loss scaling)")
         ws = list(adapter_weights)
         L = len(self.levels)
         _check_adapter_weights(ws, [(WIDTH, WIDTH)] * self.adapt_until + [(EMBED, WIDTH)] * (L + 1), self.device)
@@ -339,10 +372,13 @@ class VisualEngine:
 
     @_on_device
     def _train_forward(self, x, ws, lowest):
-        """The launches of forward_raw() + forward() in fp32 (_train_block_fwd per block), every
-        block above `lowest` writing fresh buffers. lowest = index of the lowest layer adapter
-        that needs a gradient (None: only seg_proj / det_proj train, nothing of the tower is
-        kept beyond the level taps)."""
+        """The launches of forward_raw() + forward() in the engine's dtype (_train_block_fwd per
+        block), every block above `lowest` writing fresh buffers. lowest = index of the lowest
+        layer adapter that needs a gradient (None: only seg_proj / det_proj train, nothing of the
+        tower is kept beyond the level taps). A bf16 engine reads the fp32 weights ws through
+        bf16 copies made here, as set_adapter makes them for forward()."""
+        cdt = self.dtype
+        low = cdt != torch.float32
         x = x.detach().to(self.device, torch.float32).contiguous()
         B, _, S, _ = x.shape
         g = S // PATCH
@@ -351,23 +387,31 @@ class VisualEngine:
         _check_pos(self.pos, n_tok)
         R, W, dev = B * n_tok, WIDTH, self.device
         e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
-        cols, X, H = e(B * P, KPATCH), e(R, W), e(R, W)
+        c = lambda *s: torch.empty(*s, device=dev, dtype=cdt)  # noqa: E731
+        cols, X, H = c(B * P, KPATCH), e(R, W), c(R, W)
         ops.im2col(x, cols, PATCH)
         ops.gemm(cols, self.conv, X, row_group=P, row_group_out=n_tok, row_offset=1)
         ops.embed_ln(X, self.cls, self.pos, self.ln_pre, self.blocks[0]["ln1"], H, B, n_tok)
         lvl = {lv: j for j, lv in enumerate(self.levels)}
         last, L, au = self.levels[-1], len(self.levels), self.adapt_until
-        scratch = (e(R, 3 * W), e(R, W), e(R, 4 * W), e(R, W))  # qkv, att, fc, u of the blocks without a backward
-        taps = [e(B * P, W) for _ in range(L)]
+        # qkv, att, fc, u (+ xb, the 16-bit adapter input) of the blocks without a backward
+        scratch = (c(R, 3 * W), c(R, W), c(R, 4 * W), e(R, W)) + ((c(R, W),) if low else ())
+        taps = [c(B * P, W) for _ in range(L)]
         saved, x_tap = {}, {}
-        attend = lambda qkv, att: ops.attention(qkv, att, B, n_tok, HEADS)  # noqa: E731
+        wc = [w.to(cdt) for w in ws] if low else ws  # the GEMM operands of the live fp32 weights
+        if low:
+            attend = lambda qkv, att: ops.attention(qkv, att, B, n_tok, HEADS,  # noqa: E731
+                                                    q_prescaled=self.q_prescaled)
+        else:
+            attend = lambda qkv, att: ops.attention(qkv, att, B, n_tok, HEADS)  # noqa: E731
         for i in range(last):
             keep = lowest is not None and i > lowest        # this block has a backward
             adapt = i < au
             keep_blend = lowest is not None and adapt and i >= lowest
             # attention_bwd_tiled reads the forward's output: att is kept
             X, u = _train_block_fwd(self.blocks[i], X, H, scratch, attend, keep=keep, keep_blend=keep_blend,
-                                    keep_att=True, act=self.act, w_adapt=ws[i] if adapt else None, saved=saved, i=i)
+                                    keep_att=True, act=self.act, w_adapt=wc[i] if adapt else None, saved=saved, i=i,
+                                    dtype=cdt)
             tap = taps[lvl[i + 1]] if (i + 1) in lvl else None
             nxt = self.blocks[i + 1]["ln1"] if i + 1 < last else None
             if u is not None or nxt is not None or tap is not None:
@@ -378,8 +422,8 @@ class VisualEngine:
         # projections: the level GEMMs of forward_raw (det_proj packed behind the last level)
         seg_raw = []
         for j in range(L - 1):
-            seg_raw.append(ops.gemm(taps[j], ws[au + j], e(B * P, EMBED), leaky=self.relu))
-        tail = ops.gemm(taps[L - 1], torch.cat([ws[au + L - 1], ws[au + L]], 0), e(B * P, 2 * EMBED), leaky=self.relu)
+            seg_raw.append(ops.gemm(taps[j], wc[au + j], e(B * P, EMBED), leaky=self.relu))
+        tail = ops.gemm(taps[L - 1], torch.cat([wc[au + L - 1], wc[au + L]], 0), e(B * P, 2 * EMBED), leaky=self.relu)
         seg_raw.append(tail[:, :EMBED])
         det_raw = tail[:, EMBED:]
         out = [ops.l2_normalize(s_, e(B * P, EMBED)).view(B, P, EMBED) for s_ in seg_raw]
@@ -397,8 +441,22 @@ class VisualEngine:
         R, W, dev = B * n_tok, WIDTH, self.device
         L, au, last = len(self.levels), self.adapt_until, self.levels[-1]
         e = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
-        wt = lambda w: w.detach().t().contiguous()  # noqa: E731
+        cdt = self.dtype
+        low = cdt != torch.float32
+        c = lambda *s: torch.empty(*s, device=dev, dtype=cdt)  # noqa: E731
+        wt = lambda w: w.detach().to(cdt).t().contiguous()  # noqa: E731
         grads = [None] * len(ws)
+        # mixed precision: the projection gradients and the weight-gradient kernel stay fp32; a
+        # bf16 tap is upcast exactly for it, d is copied to bf16 for the input-gradient GEMM
+        tap32 = {}
+
+        def tap_f32(lv):
+            if not low:
+                return st["taps"][lv]
+            if lv not in tap32:
+                tap32[lv] = ops.cast_rows(st["taps"][lv], dtype=torch.float32)
+            return tap32[lv]
+        d16 = c(B * P, EMBED) if low else None
         # a level's tap feeds the tower backward only if a trainable adapter lies at or below it
         flows = [lowest is not None and lv - 1 >= lowest for lv in self.levels]
         dtaps = [None] * L
@@ -415,22 +473,31 @@ class VisualEngine:
             if self.relu:
                 ops.act_bwd(d, raw.contiguous(), "leaky", out=d)
             if need[au + j]:
-                grads[au + j] = ops.linear_wgrad(d, st["taps"][lv])
+                grads[au + j] = ops.linear_wgrad(d, tap_f32(lv))
             if flows[lv]:
+                dl = ops.cast_rows(d, d16) if low else d
                 if dtaps[lv] is None:
-                    dtaps[lv] = ops.gemm(d, wt(ws[au + j]), e(B * P, W))
+                    dtaps[lv] = ops.gemm(dl, wt(ws[au + j]), e(B * P, W))
                 else:
-                    ops.gemm(d, wt(ws[au + j]), dtaps[lv], residual=dtaps[lv])
+                    ops.gemm(dl, wt(ws[au + j]), dtaps[lv], residual=dtaps[lv])
         if lowest is None:
             return grads
         if self._bwd is None:
             self._bwd = _bwd_weights(self.blocks, last)
         lvl = {lv: j for j, lv in enumerate(self.levels)}
         g = torch.zeros(R, W, device=dev, dtype=torch.float32)
-        d_qkv, d_wide, d_w, du = e(R, 3 * W), e(R, 4 * W), e(R, W), e(R, W)
-        attn_ws = ops.attention_bwd_tiled_workspace(B, n_tok, HEADS, dev)
-        attend_bwd = lambda sv, d_att, dqkv: ops.attention_bwd_tiled(  # noqa: E731
-            sv["qkv"], sv["att"], d_att, B, n_tok, HEADS, dqkv=dqkv, workspace=attn_ws)
+        d_qkv, d_wide, d_w, du = c(R, 3 * W), c(R, 4 * W), e(R, W), e(R, W)
+        if low:
+            lo, du16 = (c(R, W), c(R, W)), c(R, W)  # the 16-bit copy of g, d_att; the copy of du
+            attn_ws = ops.attention_bwd16_workspace(B, n_tok, HEADS, dev)
+            attend_bwd = lambda sv, d_att, dqkv: ops.attention_bwd16(  # noqa: E731
+                sv["qkv"], sv["att"], d_att, B, n_tok, HEADS, q_prescaled=self.q_prescaled, dqkv=dqkv,
+                workspace=attn_ws)
+        else:
+            lo = du16 = None
+            attn_ws = ops.attention_bwd_tiled_workspace(B, n_tok, HEADS, dev)
+            attend_bwd = lambda sv, d_att, dqkv: ops.attention_bwd_tiled(  # noqa: E731
+                sv["qkv"], sv["att"], d_att, B, n_tok, HEADS, dqkv=dqkv, workspace=attn_ws)
         act_mode = "quick" if self.act == "quick" else "gelu"
         taps = {}
         for i in range(last - 1, lowest - 1, -1):
@@ -438,10 +505,11 @@ class VisualEngine:
             if j is not None and dtaps[j] is not None:  # the level tap read x after block i (blend included)
                 ops.tap_ln_bwd(dtaps[j], st["x_tap"][j], self.ln_post[0], g, B, n_tok)
             sv = st["blocks"].get(i, {})
-            _blend_bwd(i, lowest, g, du, sv, ws, self.i_w, need, grads, taps if i in self.tap_blocks else None)
+            _blend_bwd(i, lowest, g, du, sv, ws, self.i_w, need, grads, taps if i in self.tap_blocks else None,
+                       du16=du16)
             if i == lowest:
                 break
-            _block_bwd(g, self.blocks[i], self._bwd[i], sv, attend_bwd, act_mode, d_qkv, d_wide, d_w)
+            _block_bwd(g, self.blocks[i], self._bwd[i], sv, attend_bwd, act_mode, d_qkv, d_wide, d_w, lo=lo)
         if self.tap_blocks:
             self.tap_records.append(dict(B=B, n_tok=n_tok, taps=taps))
         return grads

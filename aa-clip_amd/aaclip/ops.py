@@ -1031,6 +1031,119 @@ def l2_normalize_bwd(dy, x, *, group: int = 0, scale: float = 1.0, out=None):
     return out
 
 
+# ------------------------------------------------------------------------ stage-2 backward, bf16
+_H16 = (torch.bfloat16, torch.float16)
+
+
+def _c16(t, name, dtype, shape=None):
+    if t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError(f"{name} must be contiguous {dtype}" + (f" {list(shape)}" if shape is not None else ""))
+
+
+def attention_bwd16_workspace(batch: int, seq: int, heads: int, device) -> torch.Tensor:
+    nbytes = ctypes.c_size_t(0)
+    call("aaclip_attention_bwd16_workspace", batch, seq, heads, ctypes.byref(nbytes))
+    return torch.empty(int(nbytes.value) // 4, device=device, dtype=torch.float32)
+
+
+def attention_bwd16(qkv, out, dout, batch: int, seq: int, heads: int, *, q_prescaled: bool = False, dqkv=None,
+                    workspace=None):
+    """bf16 dqkv [batch*seq, 3*heads*64] of the bf16 non-causal attention core, any seq >= 1, from
+    the packed bf16 qkv, the forward's bf16 output out and bf16 dout (both [batch*seq, heads*64]).
+    q_prescaled: the q columns carry log2(e)/sqrt(64) (ops.attention's flag); the q columns of
+    dqkv are then the gradient of that prescaled q."""
+    hd = 64
+    if batch < 1 or heads < 1 or seq < 1:
+        raise ValueError("attention_bwd16 needs batch, heads and seq >= 1")
+    if batch * heads > 65535:
+        raise ValueError("attention_bwd16: batch * heads must be <= 65535")
+    bf = torch.bfloat16
+    _c16(qkv, "qkv", bf, (batch * seq, 3 * heads * hd))
+    _c16(out, "out", bf, (batch * seq, heads * hd))
+    _c16(dout, "dout", bf, (batch * seq, heads * hd))
+    if dqkv is None:
+        dqkv = torch.empty_like(qkv)
+    _c16(dqkv, "dqkv", bf, qkv.shape)
+    if dqkv.data_ptr() in (qkv.data_ptr(), out.data_ptr(), dout.data_ptr()):
+        raise ValueError("attention_bwd16: dqkv must not alias qkv, out or dout")
+    if workspace is None:
+        workspace = attention_bwd16_workspace(batch, seq, heads, qkv.device)
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous():
+        raise ValueError("attention_bwd16 workspace must be contiguous fp32")
+    for t in (qkv, out, dout, dqkv, workspace):
+        if t.data_ptr() % 16:
+            raise ValueError("attention_bwd16 operands must be 16-byte aligned")
+    _dev(qkv, out, dout, dqkv, workspace)  # after the shape / dtype checks: those need no device
+    # 2 launches: S twice + dP + dQ, and S + dP + dV + dK: 16 seq^2 hd FLOPs per (image, head)
+    _launch("visual_bwd", "attention_bwd16", 16.0 * batch * heads * seq * seq * hd,
+            (3 * qkv.numel() + 3 * dout.numel()) * 2, "aaclip_attention_bwd16", _lib.BF16, _ptr(qkv), _ptr(out),
+            _ptr(dout), _ptr(dqkv), batch, seq, heads, hd, _lib.ATTN_Q_PRESCALED if q_prescaled else 0,
+            _ptr(workspace), workspace.numel() * 4, _stream())
+    return dqkv
+
+
+def act_to16(x, mode, *, out):
+    """out (contiguous bf16 / fp16, x's shape) = f(x) of fp32 x with the 16-bit GEMM epilogue's own
+    'gelu' / 'quick' / 'leaky' and rounding."""
+    m = _act_mode(mode)
+    _f32c(x, "x")
+    if out.dtype not in _H16:
+        raise ValueError("act_to16: out must be bfloat16 or float16")
+    _c16(out, "out", out.dtype, x.shape)
+    if x.data_ptr() % 16 or out.data_ptr() % 16:
+        raise ValueError("act_to16 operands must be 16-byte aligned")
+    _dev(x, out)  # after the shape / dtype checks: those need no device
+    _launch("visual_bwd", "act_to16", 0.0, 6.0 * x.numel(), "aaclip_act_to16", m, _ptr(x), _ptr(out), dtag(out),
+            x.numel(), _stream())
+    return out
+
+
+def act_bwd16(dy, ref, mode, *, out=None):
+    """out = round(dy * f'(.)) with 16-bit dy / out and the fp32 reference value (ops.act_bwd's: the
+    pre-activation for 'gelu' / 'quick', the output for 'leaky'); out may be dy."""
+    m = _act_mode(mode)
+    if dy.dtype not in _H16:
+        raise ValueError("act_bwd16: dy must be bfloat16 or float16")
+    _c16(dy, "dy", dy.dtype)
+    _f32c(ref, "ref", dy.shape)
+    if out is None:
+        out = torch.empty_like(dy)
+    _c16(out, "out", dy.dtype, dy.shape)
+    for t in (dy, ref, out):
+        if t.data_ptr() % 16:
+            raise ValueError("act_bwd16 operands must be 16-byte aligned")
+    _dev(dy, ref, out)  # after the shape / dtype checks: those need no device
+    _launch("visual_bwd", "act_bwd16", 0.0, 8.0 * dy.numel(), "aaclip_act_bwd16", m, _ptr(dy), _ptr(ref), _ptr(out),
+            dtag(dy), dy.numel(), _stream())
+    return out
+
+
+def cast_rows(x, out=None, *, dtype=None):
+    """out = x in the other precision, row by row: fp32 -> bf16 / fp16 (round to nearest even, the GEMM
+    epilogue's conversion) or bf16 / fp16 -> fp32 (exact). 2-D, unit column stride, columns a
+    multiple of 8, 16-byte aligned rows; out (or a fresh contiguous tensor of `dtype`) is returned."""
+    _rowmajor(x, "x")
+    if out is None:
+        if dtype is None:
+            raise ValueError("cast_rows needs out or dtype")
+        out = torch.empty(x.shape, device=x.device, dtype=dtype)
+    _rowmajor(out, "out")
+    pair = (x.dtype, out.dtype)
+    if not ((pair[0] == torch.float32 and pair[1] in _H16) or (pair[0] in _H16 and pair[1] == torch.float32)):
+        raise ValueError("cast_rows converts float32 -> bfloat16 / float16 or bfloat16 / float16 -> float32")
+    if tuple(out.shape) != tuple(x.shape) or x.shape[1] % 8 or x.shape[1] == 0:
+        raise ValueError("cast_rows: out must have x's shape and the columns must be a multiple of 8")
+    for t in (x, out):
+        if (t.stride(0) * t.element_size()) % 16 or t.data_ptr() % 16 or t.stride(0) < t.shape[1]:
+            raise ValueError("cast_rows: rows must be 16-byte aligned")
+    if x.data_ptr() == out.data_ptr():
+        raise ValueError("cast_rows: out must not alias x")
+    _dev(x, out)  # after the shape / dtype checks: those need no device
+    _launch("visual_bwd", "cast_rows", 0.0, 6.0 * x.numel(), "aaclip_cast_rows", dtag(x), dtag(out), _ptr(x),
+            x.stride(0), _ptr(out), out.stride(0), x.shape[0], x.shape[1], _stream())
+    return out
+
+
 class _AnchorColumn(torch.autograd.Function):
     """One anchor column normalize(mean_s normalize(emb[s])) with a backward to emb."""
 

@@ -128,6 +128,50 @@ __device__ __forceinline__ float qgelu_exact(float v) { return v * (1.0f / (1.0f
 // nn.LeakyReLU(0.01), written as the epilogue writes it
 __device__ __forceinline__ float leaky_relu(float v) { return v >= 0.f ? v : 0.01f * v; }
 
+// ---------------------------------------------------------------- 16-bit activations
+// The forms the 16-bit GEMM epilogues apply (gemm.hip wave_epilogue / wave_epilogue_lds). Shared
+// with aaclip_act_to16 (visual_bwd16.hip), which the bf16 training forward runs on a stored fp32
+// c_fc pre-activation: the same function on the same value, so its bits are the eval path's.
+// GELU for the bf16-input kernel: v * sigmoid(v * P(v^2)), P quadratic, fitted
+// (minimax on [-12, 12]) to the erf form: |error| <= 2.6e-5 absolute, an order
+// below the bf16 rounding of the output for |y| >= 0.01. The clamp keeps the
+// quintic in its monotone range (|v| > 8: sigmoid is 0/1 to 1e-12). 7 VALU + one
+// v_exp + one v_rcp per element, vs 16 + 2 for an erfc-polynomial form; the c_fc
+// epilogue is VALU-bound (all waves of the chip run it at once, no MFMA to hide
+// behind). -log2(e) is folded into the coefficients so v_exp_f32 (2^x) applies
+// directly. The fp32 parity kernel keeps the exact erff form (gelu_erf, common.h).
+__device__ __forceinline__ float gelu_fast(float v) {
+  const float vc = __builtin_amdgcn_fmed3f(v, -8.0f, 8.0f);
+  const float s = vc * vc;
+  const float w = vc * fmaf(s, fmaf(s, 0.0010142630f, -0.10677572f), -2.3011212f);
+  return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(w));
+}
+
+// gelu_fast on a column pair in packed f32 arithmetic (v_pk_mul/v_pk_fma/v_pk_add: two
+// elements per VALU issue; the epilogue runs with no MFMA beside it, so the packed
+// forms are pure savings here): 2 v_med3 + 5 packed + 2 v_exp + 2 v_rcp per pair,
+// the same roundings as gelu_fast element by element.
+__device__ __forceinline__ float2_t gelu_fast2(float2_t v) {
+  const float2_t vc = {__builtin_amdgcn_fmed3f(v[0], -8.0f, 8.0f), __builtin_amdgcn_fmed3f(v[1], -8.0f, 8.0f)};
+  const float2_t s = vc * vc;
+  const float2_t c2 = {0.0010142630f, 0.0010142630f}, c1 = {-0.10677572f, -0.10677572f},
+                 c0 = {-2.3011212f, -2.3011212f}, one = {1.0f, 1.0f};
+  const float2_t w = vc * __builtin_elementwise_fma(s, __builtin_elementwise_fma(s, c2, c1), c0);
+  const float2_t d = float2_t{__builtin_amdgcn_exp2f(w[0]), __builtin_amdgcn_exp2f(w[1])} + one;
+  return v * float2_t{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+}
+
+// 16-bit kernels, a column pair in packed f32: v * rcp(1 + 2^(-1.702 log2(e) v)); the
+// argument is clamped to |.| <= 64 (exp2 stays finite, sigmoid is 0/1 to 1e-19 there).
+// |error| vs qgelu_exact <= 2 ulp, far below the 16-bit rounding of the output.
+__device__ __forceinline__ float2_t qgelu_fast2(float2_t v) {
+  constexpr float c = -1.702f * 1.44269504088896340736f;
+  const float2_t w = float2_t{__builtin_amdgcn_fmed3f(v[0] * c, -64.0f, 64.0f),
+                              __builtin_amdgcn_fmed3f(v[1] * c, -64.0f, 64.0f)};
+  const float2_t d = float2_t{__builtin_amdgcn_exp2f(w[0]), __builtin_amdgcn_exp2f(w[1])} + float2_t{1.0f, 1.0f};
+  return v * float2_t{__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+}
+
 // ---------------------------------------------------------------- launch checking
 #define AACLIP_CHECK_LAUNCH()                                 \
   do {                                                        \

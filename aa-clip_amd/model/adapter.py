@@ -8,7 +8,8 @@ parameters; the packed device copies are rebuilt whenever a parameter changes
 (load_state_dict, in-place edits: tracked by tensor version counters; a changed adapter is
 re-bound without repacking the frozen tower). `encode_text` under grad mode with a trainable
 `text_adapter` is differentiable into it (stage 1), and so is `forward` into a trainable
-`image_adapter` in the fp32 mode (stage 2).
+`image_adapter` in the fp32 mode (stage 2), or in bf16 mixed precision when the model is built with
+`compute_dtype=train_dtype=torch.bfloat16`.
 
 Compute dtype of the visual tower: fp16 MFMA by default — the mode that meets the
 north_star map contract (1e-3 abs + 1e-2 rel, argmax labels beyond rounding ties)
@@ -32,6 +33,14 @@ def param_signature(module: nn.Module, prefix_excl: str | None = None):
                  if prefix_excl is None or not n.startswith(prefix_excl))
 
 
+def check_train_dtype(train_dtype):
+    """train_dtype: None (stage 2 trains in the fp32 mode only) or torch.bfloat16 (it also trains
+    in bf16 mixed precision when compute_dtype is bfloat16). fp16 would need loss scaling."""
+    if train_dtype is not None and train_dtype != torch.bfloat16:
+        raise ValueError(f"train_dtype must be None or torch.bfloat16, got {train_dtype!r}")
+    return train_dtype
+
+
 def _default_dtype():
     v = os.environ.get("AACLIP_DTYPE", "fp16").lower()
     if v in ("fp8", "float8", "e4m3"):  # config C5: fp8 MX block GEMMs
@@ -48,7 +57,8 @@ def _default_dtype():
 class AdaptedCLIP(nn.Module):
     def __init__(self, clip_model, text_adapt_weight: float = 0.1, image_adapt_weight: float = 0.1,
                  text_adapt_until: int = 3, image_adapt_until: int = 6, levels: list = [6, 12, 18, 24],
-                 relu: bool = True, compute_dtype: torch.dtype | None = None, **kwargs):
+                 relu: bool = True, compute_dtype: torch.dtype | None = None,
+                 train_dtype: torch.dtype | None = None, **kwargs):
         super().__init__()
         self.clipmodel = clip_model
         self.image_encoder = clip_model.visual
@@ -58,6 +68,7 @@ class AdaptedCLIP(nn.Module):
         self.i_w = image_adapt_weight
         self.levels = list(levels)
         self.compute_dtype = compute_dtype or _default_dtype()
+        self.train_dtype = check_train_dtype(train_dtype)
         width = clip_model.visual.conv1.weight.shape[0]
         embed = clip_model.visual.output_dim
         twidth = clip_model.transformer.width
@@ -125,11 +136,14 @@ class AdaptedCLIP(nn.Module):
         Stage 2 (reference train.py:117-174): with grad mode on, compute_dtype float32 and at
         least one image_adapter weight requiring grad, the same tensors come back with a grad_fn
         into the image adapter weights, read live (VisualEngine.forward_train: the same launches
-        and bits, activations kept for the HIP backward; one chunk). Every other call -- no_grad,
-        a frozen image adapter, the 16-bit and fp8 modes even under grad -- is the forward-only
-        path, unchanged."""
+        and bits, activations kept for the HIP backward; one chunk). So they do in bf16 mixed
+        precision, for a model built with compute_dtype == train_dtype == bfloat16. Every other
+        call -- no_grad, a frozen image adapter, the 16-bit and fp8 modes without train_dtype even
+        under grad -- is the forward-only path, unchanged."""
         eng = self.visual_engine()
-        if torch.is_grad_enabled() and self.compute_dtype == torch.float32:
+        trains = self.compute_dtype == torch.float32 or (
+            self.train_dtype == torch.bfloat16 and self.compute_dtype == torch.bfloat16)
+        if torch.is_grad_enabled() and trains:
             weights = self._adapter_weights()
             if any(w.requires_grad for w in weights):
                 return eng.forward_train(x, weights)

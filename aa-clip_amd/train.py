@@ -10,8 +10,10 @@ Stage 1 (train_text_adapter, reference train.py:38-114) trains `text_adapter` ag
 surgery tower's patch features; stage 2 (train_image_adapter, :117-174) trains `image_adapter`.
 Both loop bodies are the reference's as written, including its `loss =` inside stage 1's per-level
 loop (only the last level reaches backward()), `scheduler.step()` per batch in stage 2, Adam
-betas (0.5, 0.999) and MultiStepLR [16000, 32000]. The adapted model computes in fp32 (the mode
-with a backward). Writes text_adapter.pth {epoch, text_adapter, text_optimizer}, image_adapter.pth
+betas (0.5, 0.999) and MultiStepLR [16000, 32000]. The adapted model computes in fp32; with
+AACLIP_TRAIN_DTYPE=bf16 in the environment (default fp32) stage 2 runs in bf16 mixed precision
+instead (fp32 weights, gradients, Adam and residual stream, bf16 GEMM inputs), stage 1 and the text
+anchors as before, and the checkpoints keep their keys and fp32 tensors. Writes text_adapter.pth {epoch, text_adapter, text_optimizer}, image_adapter.pth
 and image_adapter_<epoch>.pth {epoch, image_adapter, image_optimizer}; resumes from them as the
 reference does.
 
@@ -49,6 +51,16 @@ from model.clip import create_model  # noqa: E402
 from utils import setup_seed  # noqa: E402
 
 cpu_num = 4
+
+
+def train_dtype_from_env(env=None) -> torch.dtype:
+    """Stage 2's compute dtype from AACLIP_TRAIN_DTYPE: fp32 (the default) or bf16."""
+    v = (os.environ if env is None else env).get("AACLIP_TRAIN_DTYPE", "fp32").strip().lower()
+    if v in ("fp32", "float32", "f32"):
+        return torch.float32
+    if v in ("bf16", "bfloat16"):
+        return torch.bfloat16
+    raise ValueError(f"AACLIP_TRAIN_DTYPE={v!r}: expected fp32 or bf16")
 
 
 def _batches(train_loader, prep, generator, device, max_steps):
@@ -219,6 +231,7 @@ def run(args):
     """main() body; returns a context dict (the model, each stage's per-step losses, whether stage 1
     ran and the epochs both stages started from) for callers/tests."""
     setup_seed(args.seed)
+    train_dtype = train_dtype_from_env()
     if not torch.cuda.is_available():
         raise RuntimeError("the AA-CLIP MI355X build needs a GPU (no CPU path)")
     # check save_path and setting logger
@@ -320,6 +333,9 @@ def run(args):
             text_embeddings = get_adapted_text_embedding(clip_model, prompt_dataset, device)
         else:
             text_embeddings = get_adapted_text_embedding(model, prompt_dataset, device)
+    if train_dtype == torch.bfloat16:  # stage 2 in bf16 mixed precision; the tower is packed on first use
+        model.compute_dtype = model.train_dtype = torch.bfloat16
+    ctx["train_dtype"] = train_dtype
     model = train_image_adapter(model=model, text_embeddings=text_embeddings, image_epoch=args.image_epoch,
                                 train_loader=image_dataloader, optimizer=image_optimizer,
                                 scheduler=image_scheduler, device=device, start_epoch=image_start_epoch,

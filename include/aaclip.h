@@ -596,6 +596,51 @@ int aaclip_tap_ln_bwd(const float* dtap, const float* x, const float* w, float* 
 int aaclip_l2_normalize_bwd(const float* dy, int64_t lddy, int dy_group, float scale, const float* x, int64_t ldx,
                             float* dx, int64_t lddx, int rows, int width, void* stream);
 
+/* ------------------------------------------------------------------ stage-2 backward, bf16
+ * The kernels of the bf16 mixed-precision stage-2 step (visual_bwd16.hip). The residual and
+ * gradient streams, the LayerNorm / blend / normalise backwards and the weight gradients stay
+ * the fp32 entries above; every GEMM is aaclip_gemm in bf16 on the transposed packed weights.
+ *
+ * aaclip_attention_bwd16: aaclip_attention_bwd_tiled on bf16 operands (dtype must be
+ * AACLIP_BF16) and v_mfma_f32_16x16x32_bf16: packed bf16 qkv, the forward's bf16 out and bf16
+ * dout in, bf16 dqkv out; fp32 softmax statistics and accumulation. Same two launches, so
+ * deterministic, atomics-free and image local; P and dS = P (dP - D) (from the fp32 P) are
+ * rounded to bf16 before their second product. flags: 0 or AACLIP_ATTN_Q_PRESCALED (the q
+ * columns carry log2(e) / sqrt(64), as aaclip_attention): the q columns of dqkv are then the
+ * gradient of the PRESCALED q, what a GEMM on the prescaled in-projection weights expects;
+ * without it q is scaled and rounded to bf16 at load, as aaclip_attention does. dk and dv
+ * are the same either way. Non-causal, head_dim 64, any seq >= 1; at seq == 1 dq = dk = 0 and
+ * dv = dout. dqkv must not alias an input; workspace: aaclip_attention_bwd16_workspace bytes
+ * (2 * batch * heads * seq floats); all operands 16-byte aligned.
+ * Replaces: the autograd of F.multi_head_attention_forward's core under train.py:156.
+ */
+int aaclip_attention_bwd16_workspace(int batch, int seq, int heads, size_t* bytes);
+int aaclip_attention_bwd16(int dtype, const void* qkv, const void* out, const void* dout, void* dqkv, int batch,
+                           int seq, int heads, int head_dim, int flags, float* workspace, size_t workspace_bytes,
+                           void* stream);
+
+/*
+ * y = (out_dtype) f(x) on n fp32 values, f = the 16-bit GEMM epilogue's own activation of
+ * mode AACLIP_EPI_GELU / _QGELU / _LEAKY and its own rounding: a bias-only GEMM with fp32
+ * output followed by this launch gives the bits of the fused 16-bit epilogue and keeps the
+ * pre-activation. out_dtype AACLIP_BF16 or AACLIP_F16; x and y 16-byte aligned, distinct.
+ */
+int aaclip_act_to16(int mode, const float* x, void* y, int out_dtype, int64_t n, void* stream);
+
+/*
+ * aaclip_act_bwd with 16-bit dy and dx (dtype AACLIP_BF16 or AACLIP_F16; dx may be dy) and
+ * the fp32 reference value: dx = round(dy * f'(ref)), the derivative evaluated in fp32.
+ */
+int aaclip_act_bwd16(int mode, const void* dy, const float* ref, void* dx, int dtype, int64_t n, void* stream);
+
+/*
+ * y[r][c] = (out_dtype) x[r][c] for rows x cols elements: fp32 -> bf16 / fp16 (round to nearest
+ * even, the GEMM epilogue's conversion) or bf16 / fp16 -> fp32 (exact). cols a multiple of 8;
+ * ldx, ldy >= cols in elements with 16-byte aligned rows on both sides; x != y.
+ */
+int aaclip_cast_rows(int in_dtype, int out_dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int rows,
+                     int cols, void* stream);
+
 /*
  * Full test-branch anomaly map for one batch: patch_scores (mode 0) into the
  * caller's workspace grid_ws (>= batch*g*g fp32), then blur + upsample into

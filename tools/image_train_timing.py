@@ -1,6 +1,6 @@
 """Time one stage-2 step's visual forward + backward into the image adapter on an MI355X.
 
-  python tools/image_train_timing.py [--batch 2] [--img 518] [--warmup 5] [--reps 30]
+  python tools/image_train_timing.py [--batch 2] [--img 518] [--warmup 5] [--reps 30] [--dtype fp32|bf16]
                                      [--out profiles/r10/image_train_timing.json]
 
 What a stage-2 step (train.py:145-156) does on the visual side: AdaptedCLIP.forward under grad
@@ -13,7 +13,11 @@ warm-up, median (min-max) of --reps runs. The identical formula in torch-ROCm ea
 autograd (tests/imagebwd_ref.py, fp32, on the same device tensors) runs IN THE SAME PROCESS, the
 two alternating. Then the library sequence again under an ops.set_probe probe (HIP events around
 every probed launch): time per kernel name, with the achieved TFLOP/s of attention_bwd_tiled
-against the 157 TFLOP/s fp32-MFMA peak. Nothing is gated on these numbers. Needs a GPU.
+against the 157 TFLOP/s fp32-MFMA peak. --dtype bf16 times the bf16 mixed-precision step instead
+(AdaptedCLIP(compute_dtype = train_dtype = bfloat16); the eager formula stays fp32), reports
+attention_bwd16 against the 2.5 PFLOP/s bf16 dense peak and writes
+profiles/r12/image_train_timing_bf16.json by default. Both report the peak device memory of one
+library step. Nothing is gated on these numbers. Needs a GPU.
 """
 from __future__ import annotations
 
@@ -35,6 +39,7 @@ from aaclip import ops  # noqa: E402
 from oracle import synth  # noqa: E402
 
 FP32_MFMA_PEAK_TF = 157.0
+BF16_MFMA_PEAK_TF = 2500.0
 
 
 def timed(fn):
@@ -73,8 +78,12 @@ def main():
     ap.add_argument("--img", type=int, default=518)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--reps", type=int, default=30)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r10", "image_train_timing.json"))
+    ap.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.out is None:
+        a.out = (os.path.join(ROOT, "profiles", "r10", "image_train_timing.json") if a.dtype == "fp32" else
+                 os.path.join(ROOT, "profiles", "r12", "image_train_timing_bf16.json"))
     if not torch.cuda.is_available():
         raise SystemExit("image_train_timing needs an MI355X: no GPU found (nothing is measured on the CPU)")
     from model.adapter import AdaptedCLIP
@@ -84,7 +93,10 @@ def main():
     clip = create_model("ViT-L-14-336", a.img, pretrained=None, device=dev,
                         force_image_size=a.img if a.img != 336 else None)
     clip.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
-    model = AdaptedCLIP(clip, relu=False, compute_dtype=torch.float32).to(dev).eval()
+    if a.dtype == "bf16":
+        model = AdaptedCLIP(clip, relu=False, compute_dtype=torch.bfloat16, train_dtype=torch.bfloat16).to(dev).eval()
+    else:
+        model = AdaptedCLIP(clip, relu=False, compute_dtype=torch.float32).to(dev).eval()
     ia, _ = synth.adapter_state_dicts(111)
     model.image_adapter.load_state_dict({k: torch.from_numpy(v) for k, v in ia.items()})
     for p in model.parameters():
@@ -103,6 +115,15 @@ def main():
         loss = IR.fixture_loss(seg, det, G)
         loss.backward()
         return loss
+
+    # peak device memory of one library step (the packed tower, its transposes and the kept
+    # activations), before the eager formula's own copy of the weights exists
+    hip_step()
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    hip_step()
+    torch.cuda.synchronize()
+    peak_mib = round(torch.cuda.max_memory_allocated(dev) / 2 ** 20, 1)
 
     P = {k: v.to(dev) for k, v in IR.params(sd, torch.float32).items()}
     ew = [w.detach().clone().requires_grad_() for w in weights]
@@ -149,12 +170,12 @@ def main():
     n_probed = sum(k["launches"] for k in kernels.values())
     sum_us = sum(k["median_us"] for k in kernels.values())
     res = {"tool": "tools/image_train_timing.py", "device": torch.cuda.get_device_name(0), "batch": a.batch,
-           "img_size": a.img, "tokens_per_image": n_patch + 1, "dtype": "fp32", "warmup": a.warmup, "reps": a.reps,
+           "img_size": a.img, "tokens_per_image": n_patch + 1, "dtype": a.dtype, "warmup": a.warmup, "reps": a.reps,
            "method": "HIP events around one visual forward + backward, library and torch eager (fp32, autograd, same "
                      "device tensors) alternating in one process after warm-up; per-kernel times from HIP events "
                      "around every probed launch (ops.set_probe), summed per kernel name and run",
            "loss_library": float(lh.detach()), "loss_eager": float(le.detach()), "grad_rel_l2_library_vs_eager": grad_gap,
-           "library_fwd_bwd": spread(th), "eager_fwd_bwd": spread(te),
+           "library_fwd_bwd": spread(th), "eager_fwd_bwd": spread(te), "library_step_peak_memory_mib": peak_mib,
            "eager_over_library": round(statistics.median(te) / step_ms, 3),
            "kernels": kernels, "probed_launches": n_probed, "sum_of_kernel_us": round(sum_us, 1),
            "kernel_time_share_of_step": round(sum_us * 1e-3 / step_ms, 3)}
@@ -162,6 +183,10 @@ def main():
         tf = kernels["attention_bwd_tiled"]["tflops"]
         res["attention_bwd_tiled"] = {"tflops": tf, "fp32_mfma_peak_tflops": FP32_MFMA_PEAK_TF,
                                       "fraction_of_peak": round(tf / FP32_MFMA_PEAK_TF, 3)}
+    if "attention_bwd16" in kernels:
+        tf = kernels["attention_bwd16"]["tflops"]
+        res["attention_bwd16"] = {"tflops": tf, "bf16_mfma_peak_tflops": BF16_MFMA_PEAK_TF,
+                                  "fraction_of_peak": round(tf / BF16_MFMA_PEAK_TF, 3)}
     print(json.dumps({k: res[k] for k in res if k != "kernels"}))
     for name, k in kernels.items():
         print(name, json.dumps(k))
