@@ -101,6 +101,8 @@ def gemm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, bias=None, gelu
     rows_out = M if row_group == 0 else ((M - 1) // row_group) * row_group_out + row_offset + (M - 1) % row_group + 1
     if out.shape[0] < rows_out or (row_group and M % row_group):
         raise ValueError("gemm output rows too small for the row remap")
+    if out.element_size() == 2 and out.stride(0) % 8:
+        raise ValueError("gemm: a 16-bit output's row stride must be a multiple of 8 elements (16-byte stores)")
     epi, ldr, ldaux = _epilogue_flags(N, rows_out, bias, gelu, leaky, residual, aux,
                                       aux_dtype=torch.float16 if a.dtype == torch.float16 else torch.bfloat16)
     kind = f"gemm N{N} K{K}" + (" leaky" if leaky else "") + (" qgelu" if gelu == "quick" else " gelu" if gelu else "") + (" resid" if residual is not None else "")
@@ -313,6 +315,8 @@ def _epilogue_flags(N, rows_out, bias, gelu, leaky, residual, aux, aux_dtype=tor
         _rowmajor(aux, "aux")
         if aux.dtype != aux_dtype or aux.shape[1] != N or aux.shape[0] < rows_out:
             raise ValueError(f"aux must be {aux_dtype} [rows, N] (fp16 for fp16 operands, else bf16)")
+        if aux.stride(0) % 8:
+            raise ValueError("aux: the row stride must be a multiple of 8 elements (16-byte stores)")
         epi |= _lib.EPI_AUX_BF16
         ldaux = aux.stride(0)
     return epi, ldr, ldaux

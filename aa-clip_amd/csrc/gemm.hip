@@ -1368,7 +1368,10 @@ template <bool H16>
 int dispatch16(GemmArgs a, hipStream_t s) {
   const int M = a.M, N = a.N;
   if (a.K % 64 || N % 128) return AACLIP_ERR_ARG;
-  const bool fits = (int64_t)M * a.lda * 2 < (1ll << 31) && (int64_t)N * a.ldw * 2 < (1ll << 31);
+  // the 8-phase kernel needs operands its 32-bit buffer offsets reach, and its epilogue writes
+  // the aux copy only beside an fp32 C: a 16-bit C with an aux copy goes to the generic kernels
+  const bool fits = (int64_t)M * a.lda * 2 < (1ll << 31) && (int64_t)N * a.ldw * 2 < (1ll << 31) &&
+                    !(a.out_dtype != AACLIP_F32 && (a.epi & AACLIP_EPI_AUX_BF16));
   switch (choose16(H16 ? AACLIP_F16 : AACLIP_BF16, M, N, a.K, fits)) {
     case KERN_256x256: return launch_bf16<256, 256, 2, 4, 0, H16>(a, s);
     case KERN_8PH: return launch_bf16_8ph<H16>(a, s);
@@ -1455,15 +1458,24 @@ extern "C" int aaclip_gemm(int in_dtype, int out_dtype, int M, int N, int K, con
   AACLIP_REQUIRE(out_dtype == AACLIP_F32 || (in_dtype != AACLIP_F32 && out_dtype == in_dtype) ||
                  (in_dtype == AACLIP_F32 && out_dtype == AACLIP_BF16));
   AACLIP_REQUIRE(A && W && C && M >= 0 && N > 0 && K > 0);
-  AACLIP_REQUIRE(lda >= K && ldw >= K && ldc >= N && lda % 8 == 0 && ldw % 8 == 0 && ldc % 4 == 0);
+  // every 16-bit row of C and of the aux copy leaves as 16-byte stores (8 bytes on the 8-phase
+  // kernel's residual path), so those rows must start on 16 bytes: ld % 8 elements. fp32 rows
+  // (C, the residual) move as float4: ld % 4.
+  AACLIP_REQUIRE(lda >= K && ldw >= K && ldc >= N && lda % 8 == 0 && ldw % 8 == 0 &&
+                 ldc % (out_dtype == AACLIP_F32 ? 4 : 8) == 0);
   AACLIP_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)C % 16) == 0);
   AACLIP_REQUIRE(!(epilogue & AACLIP_EPI_BIAS) || bias);
   AACLIP_REQUIRE(!(epilogue & AACLIP_EPI_BIAS) || ((uintptr_t)bias % 16) == 0);
   AACLIP_REQUIRE(!(epilogue & AACLIP_EPI_RESID) || (residual && ldr >= N && ldr % 4 == 0));
-  AACLIP_REQUIRE(!(epilogue & AACLIP_EPI_AUX_BF16) || (aux && ldaux >= N && ldaux % 4 == 0));
+  AACLIP_REQUIRE(!(epilogue & AACLIP_EPI_AUX_BF16) || (aux && ldaux >= N && ldaux % 8 == 0));
   AACLIP_REQUIRE((epilogue & ~63) == 0 && (epilogue & (AACLIP_EPI_GELU | AACLIP_EPI_QGELU)) !=
                                                (AACLIP_EPI_GELU | AACLIP_EPI_QGELU));
   AACLIP_REQUIRE(row_group >= 0 && (row_group == 0 || row_group_out >= row_group));
+  // the shape rules hold for an empty batch too (M == 0 is accepted only where M > 0 would be)
+  if (in_dtype == AACLIP_F32)
+    AACLIP_REQUIRE(K % 16 == 0 && N % 64 == 0);
+  else
+    AACLIP_REQUIRE(K % 64 == 0 && N % 128 == 0);
   if (M == 0) return AACLIP_OK;
   GemmArgs a{A, W, C, bias, residual, aux, lda, ldw, ldc, ldr, ldaux, M, N, K, epilogue,
              out_dtype, row_group, row_group_out, row_offset, 0, 0, g_group_m, g_setprio, g_dbg,
@@ -1471,7 +1483,6 @@ extern "C" int aaclip_gemm(int in_dtype, int out_dtype, int M, int N, int K, con
   hipStream_t s = (hipStream_t)stream;
   if (in_dtype == AACLIP_BF16) return dispatch16<false>(a, s);
   if (in_dtype == AACLIP_F16) return dispatch16<true>(a, s);
-  AACLIP_REQUIRE(K % 16 == 0 && N % 64 == 0);
   a.tiles_m = ceil_div(M, 64);
   a.tiles_n = N / 64;
   gemm_f32_kernel<<<a.tiles_m * a.tiles_n, 256, 0, s>>>(a);

@@ -84,7 +84,10 @@ int aaclip_trace_buffer(void* records, void* counter, unsigned capacity);
  * (adapter.py:140, model/model.py:200).
  * in_dtype: A and W (bf16 -> bf16 MFMA, f16 -> f16 MFMA, f32 -> f32 MFMA).
  * out_dtype: C, either f32 or the 16-bit in_dtype.
- * K % 64 == 0 (bf16/f16) / K % 16 == 0 (f32); lda, ldw multiples of 8.
+ * K % 64 == 0, N % 128 == 0 (bf16/f16) / K % 16 == 0, N % 64 == 0 (f32), checked for
+ * M == 0 as well; lda, ldw multiples of 8. A 16-bit C and the 16-bit aux copy leave as
+ * 16-byte stores, so ldc (16-bit C) and ldaux are multiples of 8 elements; an fp32 C and
+ * the fp32 residual move as float4, so ldc (fp32 C) and ldr are multiples of 4.
  * Output row remap when row_group > 0:
  *   out_row = (m / row_group) * row_group_out + row_offset + (m % row_group)
  * (used to write patch embeddings after each image's CLS slot). The same
