@@ -1259,40 +1259,98 @@ def image_score(det_raw, batch, n_patch, partial, det=None, T=None, score=None, 
             int(normalize), _ptr(partial), _ptr(det), _ptr(score), _stream())
 
 
-def metrics_eval(pixel_preds: torch.Tensor, pixel_label: torch.Tensor, image_preds: torch.Tensor,
-                 image_label: torch.Tensor, *, medical: bool) -> list[float]:
-    """Device metrics_eval of one class (aaclip_metrics_eval): returns the unrounded
-    [pixel AUROC, pixel AP, image AUROC, image AP]. pixel_preds [N, ...] fp32 maps,
-    pixel_label same element count (nonzero = anomalous), image_* [N]."""
+def _pro_hw(pixel_preds, pixel_label):
+    """(H, W) of [n, H, W] / [n, 1, H, W] pixel tensors: the components need the image shape."""
+    def hw(t, name):
+        if t.dim() == 4 and t.shape[1] == 1:
+            return tuple(t.shape[2:])
+        if t.dim() == 3:
+            return tuple(t.shape[1:])
+        raise ValueError(f"pro=True needs {name} as [n, H, W] or [n, 1, H, W], got {tuple(t.shape)}")
+    a, b = hw(pixel_preds, "pixel_preds"), hw(pixel_label, "pixel_label")
+    if a != b:
+        raise ValueError(f"pixel_preds and pixel_label must have the same image shape, got {a} and {b}")
+    return a
+
+
+def _metrics_operands(pixel_preds, pixel_label, image_preds, image_label):
     N = pixel_preds.shape[0]
     preds = pixel_preds.reshape(N, -1).to(torch.float32).contiguous()
-    pix = preds.shape[1]
     lab = pixel_label.reshape(N, -1)
-    if lab.shape[1] != pix:
+    if lab.shape[1] != preds.shape[1]:
         raise ValueError("pixel_label and pixel_preds must have the same number of elements per image")
     lab = (lab != 0).to(torch.uint8).contiguous()
     ip = image_preds.reshape(-1).to(torch.float32).contiguous()
     il = (image_label.reshape(-1) != 0).to(torch.uint8).contiguous()
     if ip.numel() != N or il.numel() != N:
         raise ValueError("image_preds / image_label must have one entry per image")
-    with torch.cuda.device(preds.device):
-        return _metrics_eval_dev(preds, lab, ip, il, N, pix, medical).tolist()
+    return N, preds, lab, ip, il
 
 
-def metrics_eval_device(pixel_preds, pixel_label, image_preds, image_label, *, medical: bool) -> torch.Tensor:
+def metrics_eval(pixel_preds: torch.Tensor, pixel_label: torch.Tensor, image_preds: torch.Tensor,
+                 image_label: torch.Tensor, *, medical: bool, pro: bool = False,
+                 fpr_limit: float = 0.3) -> list[float]:
+    """Device metrics_eval of one class (aaclip_metrics_eval): returns the unrounded
+    [pixel AUROC, pixel AP, image AUROC, image AP]. pixel_preds [N, ...] fp32 maps,
+    pixel_label same element count (nonzero = anomalous), image_* [N]. With pro=True
+    (aaclip_metrics_eval_pro; pixel tensors [N, H, W] or [N, 1, H, W]) a fifth entry follows:
+    the pixel AUPRO up to the false-positive rate fpr_limit."""
+    return metrics_eval_device(pixel_preds, pixel_label, image_preds, image_label, medical=medical, pro=pro,
+                               fpr_limit=fpr_limit).tolist()
+
+
+def metrics_eval_device(pixel_preds, pixel_label, image_preds, image_label, *, medical: bool, pro: bool = False,
+                        fpr_limit: float = 0.3) -> torch.Tensor:
     """metrics_eval without the host sync: the device float64[4] result, read later (the
-    harness reads every class's at the end, so classes are enqueued back to back)."""
-    N = pixel_preds.shape[0]
-    preds = pixel_preds.reshape(N, -1).to(torch.float32).contiguous()
-    lab = (pixel_label.reshape(N, -1) != 0).to(torch.uint8).contiguous()
-    if lab.shape[1] != preds.shape[1]:
-        raise ValueError("pixel_label and pixel_preds must have the same number of elements per image")
-    ip = image_preds.reshape(-1).to(torch.float32).contiguous()
-    il = (image_label.reshape(-1) != 0).to(torch.uint8).contiguous()
-    if ip.numel() != N or il.numel() != N:
-        raise ValueError("image_preds / image_label must have one entry per image")
+    harness reads every class's at the end, so classes are enqueued back to back). With
+    pro=True the result is float64[5]: the same four numbers, bit for bit, and the pixel
+    AUPRO over the 8-connected components of pixel_label (aaclip_metrics_eval_pro)."""
+    if pro:
+        H, W = _pro_hw(pixel_preds, pixel_label)
+        if not 0.0 < float(fpr_limit) <= 1.0:
+            raise ValueError(f"fpr_limit must be in (0, 1], got {fpr_limit}")
+    N, preds, lab, ip, il = _metrics_operands(pixel_preds, pixel_label, image_preds, image_label)
     with torch.cuda.device(preds.device):
+        if pro:
+            return _metrics_eval_pro_dev(preds, lab, ip, il, N, H, W, medical, float(fpr_limit))
         return _metrics_eval_dev(preds, lab, ip, il, N, preds.shape[1], medical)
+
+
+def _aligned_workspace(nbytes, device):
+    ws = torch.empty(nbytes + 256, device=device, dtype=torch.uint8)
+    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256
+
+
+def _metrics_eval_pro_dev(preds, lab, ip, il, N, H, W, medical, fpr_limit):
+    _dev(preds, lab, ip, il)
+    need = ctypes.c_size_t(0)
+    call("aaclip_metrics_pro_workspace", N * H * W, N, ctypes.byref(need))
+    ws, at = _aligned_workspace(int(need.value), preds.device)
+    out = torch.empty(5, device=preds.device, dtype=torch.float64)
+    call("aaclip_metrics_eval_pro", _ptr(preds), _ptr(lab), _ptr(ip), _ptr(il), N, H, W, int(medical), fpr_limit,
+         at, need.value, _ptr(out), _stream())
+    return out
+
+
+def label_components(mask: torch.Tensor):
+    """8-connected components of mask != 0, per image (aaclip_label_components). mask: device
+    tensor [n, H, W] or [n, 1, H, W] of any dtype. Returns (labels int64 [n, H, W]: 0 for
+    background, else 1 + the smallest linear index y * W + x of the pixel's component; areas
+    int64 [n, H, W]: the pixel's component's area; counts int64 [n]: components per image)."""
+    if mask.dim() == 4 and mask.shape[1] == 1:
+        mask = mask[:, 0]
+    if mask.dim() != 3 or mask.numel() == 0:
+        raise ValueError(f"mask must be a non-empty [n, H, W] or [n, 1, H, W], got {tuple(mask.shape)}")
+    m = (mask != 0).to(torch.uint8).contiguous()
+    n, H, W = m.shape
+    with torch.cuda.device(m.device):
+        _dev(m)
+        # the C side writes uint32; int32 storage holds the same bits (labels and areas are < 2^31)
+        labels = torch.empty(n, H, W, device=m.device, dtype=torch.int32)
+        areas = torch.empty(n, H, W, device=m.device, dtype=torch.int32)
+        counts = torch.empty(n, device=m.device, dtype=torch.int32)
+        call("aaclip_label_components", _ptr(m), n, H, W, _ptr(labels), _ptr(areas), _ptr(counts), _stream())
+        return labels.to(torch.int64), areas.to(torch.int64), counts.to(torch.int64) & 0xFFFFFFFF
 
 
 def _metrics_eval_dev(preds, lab, ip, il, N, pix, medical):

@@ -24,6 +24,7 @@
       min-max normalisation, score fusion, radix-sorted exact tie-aware AUROC / AP,
       identical to sklearn after the reference's 4-decimal rounding). numpy inputs
       are copied to the device; there is no CPU path (without a GPU it raises).
+      pro=True adds the pixel AUPRO (aaclip_metrics_eval_pro), which the reference lacks.
 FocalLoss / BinaryDiceLoss as classes with non-default arguments and visualize() (cv2)
 are out of scope.
 """
@@ -241,14 +242,19 @@ def anomaly_map_multilevel(patch_features, epoch_text_feature, img_size, domain=
     return ops.anomaly_map(lv, T, out, grid, g=g, ksize=k, sigma=s, normalize=normalize)
 
 
-def metrics_eval(pixel_label, image_label, pixel_preds, image_preds, class_names: str, domain: str):
+def metrics_eval(pixel_label, image_label, pixel_preds, image_preds, class_names: str, domain: str,
+                 pro: bool = False):
     """forward_utils.py:233-280 on the device (aaclip_metrics_eval: class min-max, score
     fusion, exact tie-aware AUROC / AP). Tensors or numpy arrays; the rounding and the
-    dict layout are the reference's. There is no CPU path: without a GPU this raises."""
-    return metrics_eval_deferred(pixel_label, image_label, pixel_preds, image_preds, class_names, domain)()
+    dict layout are the reference's. There is no CPU path: without a GPU this raises.
+    pro=True adds "pixel AUPRO" (aaclip_metrics_eval_pro: the area under the per-region-overlap
+    curve up to a false-positive rate of 0.3, over the 8-connected components of pixel_label),
+    rounded like the other columns; pixel tensors are then [n, H, W] or [n, 1, H, W]."""
+    return metrics_eval_deferred(pixel_label, image_label, pixel_preds, image_preds, class_names, domain, pro=pro)()
 
 
-def metrics_eval_deferred(pixel_label, image_label, pixel_preds, image_preds, class_names: str, domain: str):
+def metrics_eval_deferred(pixel_label, image_label, pixel_preds, image_preds, class_names: str, domain: str,
+                          pro: bool = False):
     """metrics_eval enqueued on the device now, read later: returns a function that syncs
     and builds the reference's dict. The harness enqueues every class before reading any,
     so no class waits for the previous one's metrics on the host."""
@@ -260,14 +266,17 @@ def metrics_eval_deferred(pixel_label, image_label, pixel_preds, image_preds, cl
     t = [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
          for x in (pixel_preds, pixel_label, image_preds, image_label)]
     t = [x.to(dev, non_blocking=True) for x in t]
-    res = ops.metrics_eval_device(t[0], t[1], t[2], t[3], medical=(domain == "Medical"))
+    res = ops.metrics_eval_device(t[0], t[1], t[2], t[3], medical=(domain == "Medical"), pro=pro)
 
     def read():
-        pauc, pap, iauc, iap = res.tolist()
+        pauc, pap, iauc, iap, *aupro = res.tolist()
         if pauc != pauc:  # NaN: one pixel class only, sklearn raises here
             raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
-        return {"class name": class_names, "pixel AUC": round(pauc, 4) * 100, "pixel AP": round(pap, 4) * 100,
-                "image AUC": round(iauc, 4) * 100, "image AP": round(iap, 4) * 100}
+        out = {"class name": class_names, "pixel AUC": round(pauc, 4) * 100, "pixel AP": round(pap, 4) * 100,
+               "image AUC": round(iauc, 4) * 100, "image AP": round(iap, 4) * 100}
+        if pro:
+            out["pixel AUPRO"] = round(aupro[0], 4) * 100
+        return out
     return read
 
 

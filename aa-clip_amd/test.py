@@ -156,6 +156,8 @@ def parse_args(argv=None):
                              "Pillow path; the default); --no-gpu_preprocess = the Pillow transform in the workers")
     parser.add_argument("--results_json", type=str, default="",
                         help="also write the final table (rank 0) to this JSON file")
+    parser.add_argument("--pro", action="store_true",
+                        help="add the pixel AUPRO column (per-region overlap up to FPR 0.3, on the device)")
     return parser.parse_args(argv)
 
 
@@ -238,7 +240,8 @@ def run(args):
             prep = Preprocessor(args.img_size)
         with torch.no_grad():
             text_embeddings = get_adapted_text_embedding(model if adapt_text else clip_model, args.dataset, device)
-        df = DataFrame(columns=["class name", "pixel AUC", "pixel AP", "image AUC", "image AP"])
+        df = DataFrame(columns=["class name", "pixel AUC", "pixel AP", "image AUC", "image AP"]
+                       + (["pixel AUPRO"] if args.pro else []))
         pending = []
         ctx = {"model": model, "text_embeddings": text_embeddings, "classes": {}}
         for class_name, image_dataset in image_datasets.items():
@@ -265,7 +268,7 @@ def run(args):
                           class_name=class_name)
             # enqueued now, read after the loop: the next class's batches start at once
             pending.append(metrics_eval_deferred(masks, labels, preds, preds_image, class_name,
-                                                 domain=DOMAINS[args.dataset]))
+                                                 domain=DOMAINS[args.dataset], pro=args.pro))
             ctx["classes"][class_name] = (masks, labels, preds, preds_image)
         for read in pending:
             df.loc[len(df)] = Series(read())

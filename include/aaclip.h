@@ -701,6 +701,42 @@ int aaclip_metrics_eval(const float* pixel_preds, const uint8_t* pixel_label, co
                         void* workspace, size_t workspace_bytes, double* out, void* stream);
 
 /*
+ * 8-connected components of binary masks, per image (the regions of the per-region-overlap
+ * metric below; the reference has no counterpart: MVTec AD's evaluation code labels them on
+ * the host). mask [n_images, height, width] uint8, foreground = nonzero. labels [same] uint32:
+ * 0 for background, 1 + the smallest linear index y * width + x of the pixel's component within
+ * its image otherwise (canonical: independent of scheduling). areas [same] uint32: the pixel's
+ * component's area, 0 for background. n_components [n_images] uint32. Pixels never connect
+ * across the row end or between images. Union-find in global memory with atomicMin links; no
+ * loop waits for another wave, and every data-dependent loop is capped at height * width trips
+ * (a hit, which only a bug can cause, reports n_components = 0xFFFFFFFF for that image).
+ * Allocates nothing, does not sync. Needs height * width < 2^31 and
+ * n_images * height * width < 2^32 - 1. Deterministic.
+ */
+int aaclip_label_components(const uint8_t* mask, int n_images, int height, int width, uint32_t* labels,
+                            uint32_t* areas, uint32_t* n_components, void* stream);
+
+/*
+ * aaclip_metrics_eval plus the pixel AUPRO (the localisation metric of MVTec AD / VisA).
+ * out5[0..3]: what aaclip_metrics_eval gives on the same inputs, bit for bit (forward_utils.py:233-280;
+ * same keys, kernels and reduction order). out5[4]: with the class-normalised fp32 scores s, the
+ * 8-connected components r of pixel_label != 0 per image (R of them, areas |r|) and the N_ok pixels
+ * of label 0 of every image,
+ *   FPR(t) = #{ok pixels with s >= t} / N_ok,   PRO(t) = (1/R) sum_r #{p in r : s_p >= t} / |r|;
+ * the curve runs from (0, 0) through one point per distinct score in descending order to (1, 1),
+ * piecewise linear, and AUPRO = (1 / fpr_limit) * integral of PRO over FPR in [0, fpr_limit] (linear
+ * interpolation at the limit), exact at every distinct threshold, ties included. NaN when R == 0 or
+ * N_ok == 0. fpr_limit in (0, 1]; MVTec AD uses 0.3. pixel_preds / pixel_label [n_images, height,
+ * width]. workspace: caller-owned device memory, 256-B aligned, of the size
+ * aaclip_metrics_pro_workspace reports (about 32 bytes per pixel). No floating-point atomics or
+ * scans: fixed-order fp64 sums, the same bits on every launch.
+ */
+int aaclip_metrics_pro_workspace(int64_t n_pixels, int n_images, size_t* bytes);
+int aaclip_metrics_eval_pro(const float* pixel_preds, const uint8_t* pixel_label, const float* image_preds,
+                            const uint8_t* image_label, int n_images, int height, int width, int medical,
+                            double fpr_limit, void* workspace, size_t workspace_bytes, double* out5, void* stream);
+
+/*
  * Test-time preprocessing (replaces dataset/__init__.py:127-143
  * transform_x / transform_mask, i.e. Pillow's Image.resize as torchvision calls it,
  * then ToTensor + Normalize). Bit-exact with Pillow 8-bit resampling.
