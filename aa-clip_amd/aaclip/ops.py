@@ -1289,31 +1289,55 @@ def _metrics_operands(pixel_preds, pixel_label, image_preds, image_label):
 
 def metrics_eval(pixel_preds: torch.Tensor, pixel_label: torch.Tensor, image_preds: torch.Tensor,
                  image_label: torch.Tensor, *, medical: bool, pro: bool = False,
-                 fpr_limit: float = 0.3) -> list[float]:
+                 fpr_limit: float = 0.3, f1: bool = False) -> list[float]:
     """Device metrics_eval of one class (aaclip_metrics_eval): returns the unrounded
     [pixel AUROC, pixel AP, image AUROC, image AP]. pixel_preds [N, ...] fp32 maps,
     pixel_label same element count (nonzero = anomalous), image_* [N]. With pro=True
     (aaclip_metrics_eval_pro; pixel tensors [N, H, W] or [N, 1, H, W]) a fifth entry follows:
-    the pixel AUPRO up to the false-positive rate fpr_limit."""
+    the pixel AUPRO up to the false-positive rate fpr_limit. With f1=True (aaclip_metrics_eval_f1)
+    eight more follow: pixel F1-max, its threshold, precision and recall there, and the same four
+    for images; thresholds are in the normalised score domains (see metrics_eval_device)."""
     return metrics_eval_device(pixel_preds, pixel_label, image_preds, image_label, medical=medical, pro=pro,
-                               fpr_limit=fpr_limit).tolist()
+                               fpr_limit=fpr_limit, f1=f1).tolist()
 
 
 def metrics_eval_device(pixel_preds, pixel_label, image_preds, image_label, *, medical: bool, pro: bool = False,
-                        fpr_limit: float = 0.3) -> torch.Tensor:
+                        fpr_limit: float = 0.3, f1: bool = False) -> torch.Tensor:
     """metrics_eval without the host sync: the device float64[4] result, read later (the
     harness reads every class's at the end, so classes are enqueued back to back). With
     pro=True the result is float64[5]: the same four numbers, bit for bit, and the pixel
-    AUPRO over the 8-connected components of pixel_label (aaclip_metrics_eval_pro)."""
+    AUPRO over the 8-connected components of pixel_label (aaclip_metrics_eval_pro).
+    With f1=True (aaclip_metrics_eval_f1) the same 4 (or 5) numbers, bit for bit, are followed by
+    pixel F1-max, threshold, precision, recall and image F1-max, threshold, precision, recall:
+    float64[12] (or [13]). F1(t) = 2 TP / (PP + P) over the distinct scores t, the threshold the
+    lowest maximiser; pixel thresholds are class-normalised map values, image thresholds fused
+    image scores, both as the device computes them in fp32. Flattened [N, pix] maps stay legal
+    unless pro=True."""
     if pro:
         H, W = _pro_hw(pixel_preds, pixel_label)
         if not 0.0 < float(fpr_limit) <= 1.0:
             raise ValueError(f"fpr_limit must be in (0, 1], got {fpr_limit}")
     N, preds, lab, ip, il = _metrics_operands(pixel_preds, pixel_label, image_preds, image_label)
     with torch.cuda.device(preds.device):
+        if f1:
+            if not pro:
+                H, W = 1, preds.shape[1]  # no labelling: only H * W matters
+            out = _metrics_eval_f1_dev(preds, lab, ip, il, N, H, W, medical, pro, float(fpr_limit))
+            return out if pro else torch.cat([out[:4], out[5:]])
         if pro:
             return _metrics_eval_pro_dev(preds, lab, ip, il, N, H, W, medical, float(fpr_limit))
         return _metrics_eval_dev(preds, lab, ip, il, N, preds.shape[1], medical)
+
+
+def _metrics_eval_f1_dev(preds, lab, ip, il, N, H, W, medical, pro, fpr_limit):
+    _dev(preds, lab, ip, il)
+    need = ctypes.c_size_t(0)
+    call("aaclip_metrics_f1_workspace", N * H * W, N, int(pro), ctypes.byref(need))
+    ws, at = _aligned_workspace(int(need.value), preds.device)
+    out = torch.empty(13, device=preds.device, dtype=torch.float64)
+    call("aaclip_metrics_eval_f1", _ptr(preds), _ptr(lab), _ptr(ip), _ptr(il), N, H, W, int(medical), int(pro),
+         fpr_limit, at, need.value, _ptr(out), _stream())
+    return out
 
 
 def _aligned_workspace(nbytes, device):

@@ -24,7 +24,8 @@
       min-max normalisation, score fusion, radix-sorted exact tie-aware AUROC / AP,
       identical to sklearn after the reference's 4-decimal rounding). numpy inputs
       are copied to the device; there is no CPU path (without a GPU it raises).
-      pro=True adds the pixel AUPRO (aaclip_metrics_eval_pro), which the reference lacks.
+      pro=True adds the pixel AUPRO (aaclip_metrics_eval_pro), which the reference lacks;
+      f1=True adds pixel and image F1-max and their thresholds (aaclip_metrics_eval_f1).
 FocalLoss / BinaryDiceLoss as classes with non-default arguments and visualize() (cv2)
 are out of scope.
 """
@@ -243,21 +244,62 @@ def anomaly_map_multilevel(patch_features, epoch_text_feature, img_size, domain=
 
 
 def metrics_eval(pixel_label, image_label, pixel_preds, image_preds, class_names: str, domain: str,
-                 pro: bool = False):
+                 pro: bool = False, f1: bool = False):
     """forward_utils.py:233-280 on the device (aaclip_metrics_eval: class min-max, score
     fusion, exact tie-aware AUROC / AP). Tensors or numpy arrays; the rounding and the
     dict layout are the reference's. There is no CPU path: without a GPU this raises.
     pro=True adds "pixel AUPRO" (aaclip_metrics_eval_pro: the area under the per-region-overlap
     curve up to a false-positive rate of 0.3, over the 8-connected components of pixel_label),
-    rounded like the other columns; pixel tensors are then [n, H, W] or [n, 1, H, W]."""
-    return metrics_eval_deferred(pixel_label, image_label, pixel_preds, image_preds, class_names, domain, pro=pro)()
+    rounded like the other columns; pixel tensors are then [n, H, W] or [n, 1, H, W].
+    f1=True adds "pixel F1-max" and "image F1-max" (aaclip_metrics_eval_f1: the maximum over the
+    distinct scores t of 2 TP / (PP + P)), after "pixel AUPRO" when that is present and rounded
+    like the other columns. The thresholds that reach them are in metrics_eval_deferred(...).values()."""
+    return metrics_eval_deferred(pixel_label, image_label, pixel_preds, image_preds, class_names, domain, pro=pro,
+                                 f1=f1)()
+
+
+_F1_NAMES = [f"{level} F1{what}" for level in ("pixel", "image") for what in ("-max", " threshold", " precision",
+                                                                             " recall")]
+
+
+class _DeferredMetrics:
+    """One class's metrics, enqueued on the device: call it for the reference's dict, or read
+    values() for every computed number."""
+
+    def __init__(self, res, class_names, pro, f1):
+        self._res, self._class_names, self._pro, self._f1 = res, class_names, pro, f1
+
+    def values(self):
+        """Sync and return every computed number, unrounded (fractions, not per cent), by name:
+        "pixel AUC", "pixel AP", "image AUC", "image AP", with pro "pixel AUPRO", with f1
+        "pixel F1-max", "pixel F1 threshold", "pixel F1 precision", "pixel F1 recall" and the
+        four "image F1 ..." counterparts. Thresholds are in the normalised score domains: the
+        class min-max normalised map value (fp32; the raw value when the class maximum is 1) for
+        pixels, the fused image score (the normalised map maximum for Medical, else the mean of
+        that and the normalised image score) for images; a score >= threshold is a detection.
+        The pixel numbers are NaN when pixel_label holds one class only."""
+        names = ["pixel AUC", "pixel AP", "image AUC", "image AP"] + (["pixel AUPRO"] if self._pro else []) \
+            + (_F1_NAMES if self._f1 else [])
+        return dict(zip(names, self._res.tolist()))
+
+    def __call__(self):
+        v = self.values()
+        if v["pixel AUC"] != v["pixel AUC"]:  # NaN: one pixel class only, sklearn raises here
+            raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+        out = {"class name": self._class_names}
+        for k in ["pixel AUC", "pixel AP", "image AUC", "image AP"] + (["pixel AUPRO"] if self._pro else []) \
+                + (["pixel F1-max", "image F1-max"] if self._f1 else []):
+            out[k] = round(v[k], 4) * 100
+        return out
 
 
 def metrics_eval_deferred(pixel_label, image_label, pixel_preds, image_preds, class_names: str, domain: str,
-                          pro: bool = False):
-    """metrics_eval enqueued on the device now, read later: returns a function that syncs
+                          pro: bool = False, f1: bool = False):
+    """metrics_eval enqueued on the device now, read later: returns a callable that syncs
     and builds the reference's dict. The harness enqueues every class before reading any,
-    so no class waits for the previous one's metrics on the host."""
+    so no class waits for the previous one's metrics on the host. The returned object also has
+    .values(): every computed number unrounded, by name, among them with f1=True the F1
+    thresholds, precisions and recalls (thresholds in the normalised score domains, see there)."""
     if not torch.cuda.is_available():
         raise RuntimeError("metrics_eval runs on the MI355X kernels (aaclip_metrics_eval); no GPU is visible "
                            "and there is no CPU path")
@@ -266,18 +308,8 @@ def metrics_eval_deferred(pixel_label, image_label, pixel_preds, image_preds, cl
     t = [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
          for x in (pixel_preds, pixel_label, image_preds, image_label)]
     t = [x.to(dev, non_blocking=True) for x in t]
-    res = ops.metrics_eval_device(t[0], t[1], t[2], t[3], medical=(domain == "Medical"), pro=pro)
-
-    def read():
-        pauc, pap, iauc, iap, *aupro = res.tolist()
-        if pauc != pauc:  # NaN: one pixel class only, sklearn raises here
-            raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
-        out = {"class name": class_names, "pixel AUC": round(pauc, 4) * 100, "pixel AP": round(pap, 4) * 100,
-               "image AUC": round(iauc, 4) * 100, "image AP": round(iap, 4) * 100}
-        if pro:
-            out["pixel AUPRO"] = round(aupro[0], 4) * 100
-        return out
-    return read
+    res = ops.metrics_eval_device(t[0], t[1], t[2], t[3], medical=(domain == "Medical"), pro=pro, f1=f1)
+    return _DeferredMetrics(res, class_names, pro, f1)
 
 
 def visualize(pixel_label, pixel_preds, file_names, save_dir, dataset_name, class_name):

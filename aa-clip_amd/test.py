@@ -158,6 +158,9 @@ def parse_args(argv=None):
                         help="also write the final table (rank 0) to this JSON file")
     parser.add_argument("--pro", action="store_true",
                         help="add the pixel AUPRO column (per-region overlap up to FPR 0.3, on the device)")
+    parser.add_argument("--f1", action="store_true",
+                        help="add the pixel and image F1-max columns and log each class's operating points "
+                             "(threshold, precision, recall; thresholds in the normalised score domains)")
     return parser.parse_args(argv)
 
 
@@ -167,7 +170,9 @@ def main(argv=None):
 
 def run(args):
     """main() body; returns (results DataFrame, context dict with the model, the text
-    anchors and every class's (masks, labels, preds, preds_image)) for callers/tests."""
+    anchors and every class's (masks, labels, preds, preds_image), with --f1 also
+    "operating_points": per class the pixel and image F1-max threshold, precision and
+    recall) for callers/tests."""
     setup_seed(args.seed)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -241,9 +246,12 @@ def run(args):
         with torch.no_grad():
             text_embeddings = get_adapted_text_embedding(model if adapt_text else clip_model, args.dataset, device)
         df = DataFrame(columns=["class name", "pixel AUC", "pixel AP", "image AUC", "image AP"]
-                       + (["pixel AUPRO"] if args.pro else []))
+                       + (["pixel AUPRO"] if args.pro else [])
+                       + (["pixel F1-max", "image F1-max"] if args.f1 else []))
         pending = []
         ctx = {"model": model, "text_embeddings": text_embeddings, "classes": {}}
+        if args.f1:
+            ctx["operating_points"] = {}
         for class_name, image_dataset in image_datasets.items():
             workers = 0 if synthetic else 4
             from dataset import collate_raw
@@ -268,10 +276,19 @@ def run(args):
                           class_name=class_name)
             # enqueued now, read after the loop: the next class's batches start at once
             pending.append(metrics_eval_deferred(masks, labels, preds, preds_image, class_name,
-                                                 domain=DOMAINS[args.dataset], pro=args.pro))
+                                                 domain=DOMAINS[args.dataset], pro=args.pro, f1=args.f1))
             ctx["classes"][class_name] = (masks, labels, preds, preds_image)
         for read in pending:
-            df.loc[len(df)] = Series(read())
+            row = read()
+            df.loc[len(df)] = Series(row)
+            if args.f1:
+                v = read.values()
+                op = {level: {k: v[f"{level} F1 {k}"] for k in ("threshold", "precision", "recall")}
+                      for level in ("pixel", "image")}
+                ctx["operating_points"][row["class name"]] = op
+                logger.info("%s F1-max operating points: %s", row["class name"], "; ".join(
+                    "%s threshold %.6g, precision %.4f, recall %.4f" % (level, p["threshold"], p["precision"],
+                                                                        p["recall"]) for level, p in op.items()))
         if rank != 0:
             continue
         df.loc[len(df)] = df.drop(columns=["class name"]).mean()
@@ -281,8 +298,10 @@ def run(args):
         if args.results_json:  # the table as JSON (tests compare sharded and single-process runs)
             import json
             with open(args.results_json, "w") as f:
-                json.dump({"world": world, "rows": df.astype({c: float for c in df.columns[1:]}).to_dict("records")},
-                          f)
+                table = {"world": world, "rows": df.astype({c: float for c in df.columns[1:]}).to_dict("records")}
+                if args.f1:
+                    table["operating_points"] = ctx["operating_points"]
+                json.dump(table, f)
     return df, ctx
 
 

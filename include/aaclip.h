@@ -737,6 +737,37 @@ int aaclip_metrics_eval_pro(const float* pixel_preds, const uint8_t* pixel_label
                             double fpr_limit, void* workspace, size_t workspace_bytes, double* out5, void* stream);
 
 /*
+ * aaclip_metrics_eval plus F1-max and the score at which it is reached, for pixels and for images
+ * (the column WinCLIP, APRIL-GAN / VAND and AdaCLIP report; the reference, forward_utils.py:233-280,
+ * has no counterpart). out13[0..3]: what aaclip_metrics_eval gives on the same inputs, bit for bit.
+ * out13[4]: the AUPRO of aaclip_metrics_eval_pro when with_pro != 0, else NaN (no component labelling
+ * runs then, fpr_limit is ignored and only height * width matters). out13[5..8]: pixel F1-max, its
+ * threshold, and the precision and recall there. out13[9..12]: the same four numbers for images.
+ * With v the class-normalised fp32 map value that the sort keys are built from ((x - min) / (max - min)
+ * when the class maximum is not 1, else x), y the label (!= 0), n the pixel count and P the positives,
+ * every distinct score t has
+ *   PP(t) = #{v >= t},   TP(t) = #{y = 1, v >= t},   F1(t) = (double)(2 TP) / (double)(PP + P):
+ * two exact integers and one IEEE fp64 division. F1-max is the maximum over t; the threshold is the
+ * LOWEST t whose F1 equals it (thresholds[argmax] on sklearn's ascending precision_recall_curve
+ * thresholds, as the VAND code takes it), returned as the fp32 value widened to double; precision is
+ * TP / PP and recall TP / P at that t, one fp64 division each. Images: the same over the fused fp32
+ * image scores (the normalised row maximum when medical != 0, else 0.5 * that + 0.5 * the normalised
+ * image score) and image_label. Thresholds are therefore in the normalised score domains, not in the
+ * domain of the inputs. The pixel numbers are NaN when all pixel labels are equal (where out13[0] is
+ * NaN); the image numbers are 0 when all image labels are equal (as out13[2..3]). One more pass over
+ * the sorted positions and one O(n_images^2) kernel: no second sort, no atomics, fixed-order
+ * reductions with ties to the lower score, the same bits on every launch. workspace: caller-owned
+ * device memory, 256-B aligned, of the size aaclip_metrics_f1_workspace reports for the same with_pro.
+ * Needs height * width < 2^31 and n_images * height * width < 2^32 - 1; fpr_limit in (0, 1] when
+ * with_pro != 0.
+ */
+int aaclip_metrics_f1_workspace(int64_t n_pixels, int n_images, int with_pro, size_t* bytes);
+int aaclip_metrics_eval_f1(const float* pixel_preds, const uint8_t* pixel_label, const float* image_preds,
+                           const uint8_t* image_label, int n_images, int height, int width, int medical,
+                           int with_pro, double fpr_limit, void* workspace, size_t workspace_bytes, double* out13,
+                           void* stream);
+
+/*
  * Test-time preprocessing (replaces dataset/__init__.py:127-143
  * transform_x / transform_mask, i.e. Pillow's Image.resize as torchvision calls it,
  * then ToTensor + Normalize). Bit-exact with Pillow 8-bit resampling.
