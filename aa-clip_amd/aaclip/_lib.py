@@ -94,6 +94,9 @@ SIGNATURES = {
     "aaclip_metrics_eval_pro": [_P, _P, _P, _P, _I, _I, _I, _I, ctypes.c_double, _P, ctypes.c_size_t, _P, _P],
     "aaclip_metrics_f1_workspace": [_L, _I, _I, ctypes.POINTER(ctypes.c_size_t)],
     "aaclip_metrics_eval_f1": [_P, _P, _P, _P, _I, _I, _I, _I, _I, ctypes.c_double, _P, ctypes.c_size_t, _P, _P],
+    "aaclip_regions_workspace": [_L, _I, ctypes.POINTER(ctypes.c_size_t)],
+    "aaclip_extract_regions": [_P, _P, _I, _I, _I, _F, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P,
+                               _P],
     "aaclip_bicubic_taps": [_I, _I, ctypes.POINTER(_I)],
     "aaclip_bicubic_plan": [_I, _I, _P, _P, _I],
     "aaclip_nearest_plan": [_I, _I, _P],

@@ -1377,6 +1377,59 @@ def label_components(mask: torch.Tensor):
         return labels.to(torch.int64), areas.to(torch.int64), counts.to(torch.int64) & 0xFFFFFFFF
 
 
+def extract_regions(pixel_preds, threshold, *, pixel_label=None, normalise=True, min_area=1, max_regions=64):
+    """The defect regions of one class's maps (aaclip_extract_regions): the 8-connected components of
+    the pixels with v >= threshold, v the class-normalised fp32 map value of the metrics
+    (normalise=True: threshold may be the "pixel F1 threshold" of metrics_eval_device(f1=True)) or
+    the raw value (normalise=False). pixel_preds: device tensor [n, H, W] or [n, 1, H, W];
+    pixel_label: the same shape (nonzero = anomalous) or None. Regions under min_area pixels are
+    dropped. Returns device tensors, enqueued without a host sync, as a dict:
+      "n_regions" int64 [n]        regions left per image (may exceed max_regions; 0xFFFFFFFF when
+                                   the labelling hit a cap)
+    and per slot [n, max_regions], an image's regions first, by area descending then label
+    ascending, zero past min(n_regions, max_regions):
+      "label" int64       1 + the smallest linear index y * W + x of the region
+      "area" int64        pixels
+      "bbox" int64 [.., 4]      x0, y0, x1, y1, inclusive
+      "centroid" float64 [.., 2]  cx, cy = sum x / area, sum y / area (exact sums, one division each)
+      "peak" float32      the maximum v
+      "peak_index" int64  the smallest linear index that reaches it
+      "gt_area" int64     pixels of the region with pixel_label != 0 (0 without pixel_label)"""
+    if pixel_preds.dim() == 4 and pixel_preds.shape[1] == 1:
+        pixel_preds = pixel_preds[:, 0]
+    if pixel_preds.dim() != 3 or pixel_preds.numel() == 0:
+        raise ValueError(f"pixel_preds must be a non-empty [n, H, W] or [n, 1, H, W], got {tuple(pixel_preds.shape)}")
+    if int(min_area) < 1 or int(max_regions) < 1:
+        raise ValueError(f"min_area and max_regions must be at least 1, got {min_area} and {max_regions}")
+    preds = pixel_preds.to(torch.float32).contiguous()
+    n, H, W = preds.shape
+    lab = None
+    if pixel_label is not None:
+        if pixel_label.dim() == 4 and pixel_label.shape[1] == 1:
+            pixel_label = pixel_label[:, 0]
+        if tuple(pixel_label.shape) != (n, H, W):
+            raise ValueError(f"pixel_label must match pixel_preds {(n, H, W)}, got {tuple(pixel_label.shape)}")
+        lab = (pixel_label != 0).to(torch.uint8).contiguous()
+    R = int(max_regions)
+    with torch.cuda.device(preds.device):
+        _dev(preds, lab)
+        need = ctypes.c_size_t(0)
+        call("aaclip_regions_workspace", n * H * W, n, ctypes.byref(need))
+        ws, at = _aligned_workspace(int(need.value), preds.device)
+        # the C side writes uint32; int32 storage holds the same bits
+        i32 = {k: torch.empty(shape, device=preds.device, dtype=torch.int32)
+               for k, shape in (("n_regions", (n,)), ("label", (n, R)), ("area", (n, R)), ("bbox", (n, R, 4)),
+                                ("peak_index", (n, R)), ("gt_area", (n, R)))}
+        centroid = torch.empty(n, R, 2, device=preds.device, dtype=torch.float64)
+        peak = torch.empty(n, R, device=preds.device, dtype=torch.float32)
+        call("aaclip_extract_regions", _ptr(preds), _ptr(lab), n, H, W, float(threshold), int(bool(normalise)),
+             int(min_area), R, at, need.value, _ptr(i32["n_regions"]), _ptr(i32["label"]), _ptr(i32["area"]),
+             _ptr(i32["bbox"]), _ptr(centroid), _ptr(peak), _ptr(i32["peak_index"]), _ptr(i32["gt_area"]), _stream())
+        out = {k: v.to(torch.int64) & 0xFFFFFFFF for k, v in i32.items()}
+        out["centroid"], out["peak"] = centroid, peak
+        return out
+
+
 def _metrics_eval_dev(preds, lab, ip, il, N, pix, medical):
     _dev(preds, lab, ip, il)
     need = ctypes.c_size_t(0)

@@ -8,7 +8,8 @@
 //   merge     the same waves union each run with the segment to its left and with the row
 //             above (N, or NW / NE where N is background), once per contact.
 //   compress  every pixel finds its root; the root's area word and the image's component
-//             count are integer atomicAdds (order-free sums: deterministic).
+//             count are integer atomicAdds (order-free sums: deterministic), the count
+//             gathered per wave over a span of pixels first.
 //   publish   labels = 1 + root (the component's smallest linear index: links only ever
 //             point from a larger index to a smaller one, so the root is canonical),
 //             areas = the root's area.
@@ -22,10 +23,10 @@
 // the image's count (a count is < 2^31), published as 0xFFFFFFFF: a bug ends in a wrong
 // number, never in a hang.
 #include "common.h"
+#include "rowseg.h"
 
 namespace {
 
-constexpr int CT = 256;  // threads per block: four row-segment waves
 constexpr uint32_t BG = 0xFFFFFFFFu;
 constexpr uint32_t CAP_HIT = 0x80000000u;
 
@@ -62,27 +63,6 @@ __device__ __forceinline__ void unite(uint32_t* par, uint32_t a, uint32_t b, uin
   capped = true;
 }
 
-struct Segment {  // the row segment of this wave
-  bool valid;
-  int img, y, x0, lane;
-  size_t base;  // first pixel of the image
-};
-
-__device__ __forceinline__ Segment my_segment(int n, int H, int W) {
-  const int segs = (W + 63) >> 6;
-  const int64_t sid = (int64_t)blockIdx.x * (CT / 64) + (threadIdx.x >> 6);
-  const int64_t per_img = (int64_t)H * segs;
-  Segment s;
-  s.valid = sid < (int64_t)n * per_img;
-  s.img = s.valid ? (int)(sid / per_img) : 0;
-  const int64_t rem = s.valid ? sid % per_img : 0;
-  s.y = (int)(rem / segs);
-  s.x0 = (int)(rem % segs) << 6;
-  s.lane = threadIdx.x & 63;
-  s.base = (size_t)s.img * ((size_t)H * W);
-  return s;
-}
-
 __global__ __launch_bounds__(CT) void cc_init_kernel(const uint8_t* __restrict__ mask, int n, int H, int W,
                                                      uint32_t* __restrict__ par, uint32_t* __restrict__ areas,
                                                      uint32_t* __restrict__ counts) {
@@ -95,11 +75,7 @@ __global__ __launch_bounds__(CT) void cc_init_kernel(const uint8_t* __restrict__
   const uint64_t row = __ballot(fg);
   if (in) {
     uint32_t p = BG;
-    if (fg) {  // first pixel of this lane's run: one past the highest background bit below the lane
-      const uint64_t gaps = ~row & ((1ull << s.lane) - 1ull);
-      const int start = gaps ? 64 - __clzll(gaps) : 0;
-      p = (uint32_t)(s.y * W + s.x0 + start);
-    }
+    if (fg) p = (uint32_t)(s.y * W + s.x0 + run_start(row, s.lane));  // first pixel of this lane's run
     par[at] = p;
     areas[at] = 0u;
   }
@@ -144,35 +120,60 @@ __global__ __launch_bounds__(CT) void cc_merge_kernel(const uint8_t* __restrict_
   if (capped) atomicOr(counts + s.img, CAP_HIT);
 }
 
-// One thread per pixel of the class. Parents become roots; each wave adds its pixels to their
-// roots' area words, one atomicAdd per distinct root in the wave.
-__global__ __launch_bounds__(CT) void cc_compress_kernel(int64_t total, uint32_t hw, uint32_t* __restrict__ parents,
+// Every wave walks a contiguous span of the class's pixels, 64 at a time (`span` is a multiple of
+// 64). Parents become roots; each wave adds its pixels to their roots' area words, one atomicAdd per
+// distinct root in the 64 pixels. The roots it meets are counted in a register and added to the
+// image's count when the span leaves the image or ends: a few adds per wave, where one add per
+// root put every component of an image in line on one address (thousands, when a threshold leaves
+// a noisy map in specks).
+__global__ __launch_bounds__(CT) void cc_compress_kernel(int64_t total, uint32_t hw, int64_t span,
+                                                         uint32_t* __restrict__ parents,
                                                          uint32_t* __restrict__ areas,
                                                          uint32_t* __restrict__ counts) {
-  const int64_t i = (int64_t)blockIdx.x * CT + threadIdx.x;
   const int lane = threadIdx.x & 63;
-  const bool in = i < total;
-  const uint32_t img = in ? (uint32_t)(i / hw) : 0u;
-  const uint32_t p = in ? (uint32_t)(i - (int64_t)img * hw) : 0u;
-  const size_t base = (size_t)img * hw;
-  const bool fg = in && parent_load(parents + base + p) != BG;
-  uint32_t groot = BG;  // root as an index into the whole class (n * H * W < 2^32 - 1)
-  if (fg) {
-    bool capped = false;
-    const uint32_t r = find_root(parents + base, p, hw, capped);
-    __hip_atomic_store(parents + base + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    groot = (uint32_t)(base + r);
-    if (r == p) atomicAdd(counts + img, 1u);
-    if (capped) atomicOr(counts + img, CAP_HIT);
+  const int64_t begin = ((int64_t)blockIdx.x * (CT / 64) + (threadIdx.x >> 6)) * span;
+  const int64_t end = begin + span < total ? begin + span : total;
+  uint32_t held_img = 0u, held = 0u;  // wave-uniform: roots seen in held_img and not yet added
+  for (int64_t at = begin; at < end; at += 64) {  // wave-uniform
+    const int64_t i = at + lane;
+    const bool in = i < end;
+    const uint32_t img = in ? (uint32_t)(i / hw) : 0u;
+    const uint32_t p = in ? (uint32_t)(i - (int64_t)img * hw) : 0u;
+    const size_t base = (size_t)img * hw;
+    const bool fg = in && parent_load(parents + base + p) != BG;
+    uint32_t groot = BG;  // root as an index into the whole class (n * H * W < 2^32 - 1)
+    bool is_root = false;
+    if (fg) {
+      bool capped = false;
+      const uint32_t r = find_root(parents + base, p, hw, capped);
+      __hip_atomic_store(parents + base + p, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      groot = (uint32_t)(base + r);
+      is_root = r == p;
+      if (capped) atomicOr(counts + img, CAP_HIT);
+    }
+    uint64_t todo = __ballot(fg);
+    while (todo) {  // wave-uniform; every trip retires at least the leader
+      const int lead = __ffsll((unsigned long long)todo) - 1;
+      const uint32_t r0 = __shfl(groot, lead, 64);
+      const uint64_t same = __ballot(fg && groot == r0);
+      if (lane == lead) atomicAdd(areas + r0, (uint32_t)__popcll(same));
+      todo &= ~same;
+    }
+    uint64_t roots = __ballot(is_root);
+    while (roots) {  // wave-uniform; one trip per image among the 64 pixels' roots
+      const int lead = __ffsll((unsigned long long)roots) - 1;
+      const uint32_t im = __shfl(img, lead, 64);
+      const uint64_t same = __ballot(is_root && img == im);
+      if (im != held_img) {
+        if (held && lane == 0) atomicAdd(counts + held_img, held);
+        held_img = im;
+        held = 0u;
+      }
+      held += (uint32_t)__popcll(same);
+      roots &= ~same;
+    }
   }
-  uint64_t todo = __ballot(fg);
-  while (todo) {  // wave-uniform; every trip retires at least the leader
-    const int lead = __ffsll((unsigned long long)todo) - 1;
-    const uint32_t r0 = __shfl(groot, lead, 64);
-    const uint64_t same = __ballot(fg && groot == r0);
-    if (lane == lead) atomicAdd(areas + r0, (uint32_t)__popcll(same));
-    todo &= ~same;
-  }
+  if (held && lane == 0) atomicAdd(counts + held_img, held);
 }
 
 __global__ __launch_bounds__(CT) void cc_publish_kernel(int64_t total, uint32_t hw, uint32_t* __restrict__ labels,
@@ -208,7 +209,10 @@ extern "C" int aaclip_label_components(const uint8_t* mask, int n_images, int he
   const unsigned pix_grid = (unsigned)((total + CT - 1) / CT);
   cc_init_kernel<<<seg_grid, CT, 0, s>>>(mask, n_images, height, width, labels, areas, n_components);
   cc_merge_kernel<<<seg_grid, CT, 0, s>>>(mask, n_images, height, width, labels, n_components);
-  cc_compress_kernel<<<pix_grid, CT, 0, s>>>(total, (uint32_t)hw, labels, areas, n_components);
+  // 8192 waves at most, each over a 64-aligned span: a count takes a few adds per wave
+  const int64_t span = ((total + 8192 * 64 - 1) / (8192 * 64)) * 64;
+  const unsigned span_grid = (unsigned)(((total + span - 1) / span + CT / 64 - 1) / (CT / 64));
+  cc_compress_kernel<<<span_grid, CT, 0, s>>>(total, (uint32_t)hw, span, labels, areas, n_components);
   cc_publish_kernel<<<pix_grid, CT, 0, s>>>(total, (uint32_t)hw, labels, areas, n_components);
   AACLIP_CHECK_LAUNCH();
   return AACLIP_OK;

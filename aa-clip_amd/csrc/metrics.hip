@@ -21,55 +21,9 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "common.h"
+#include "scorenorm.h"
 
 namespace {
-
-constexpr int MT = 256;  // threads per block for the element-wise passes
-
-__device__ __forceinline__ float block_min(float v, float* sh) {
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  __syncthreads();
-  if (l == 0) sh[w] = v;
-  __syncthreads();
-  v = sh[0];
-  for (int i = 1; i < (int)(blockDim.x >> 6); ++i) v = fminf(v, sh[i]);
-  return v;
-}
-__device__ __forceinline__ float block_max(float v, float* sh) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-  __syncthreads();
-  if (l == 0) sh[w] = v;
-  __syncthreads();
-  v = sh[0];
-  for (int i = 1; i < (int)(blockDim.x >> 6); ++i) v = fmaxf(v, sh[i]);
-  return v;
-}
-
-// per-image min / max of the raw maps (one block per image)
-__global__ __launch_bounds__(MT) void row_minmax_kernel(const float* __restrict__ p, int64_t pix,
-                                                        float* __restrict__ rmin, float* __restrict__ rmax) {
-  __shared__ float sh[MT / 64];
-  const float* row = p + (size_t)blockIdx.x * pix;
-  float lo = INFINITY, hi = -INFINITY;
-  for (int64_t i = threadIdx.x; i < pix; i += MT) {
-    const float v = row[i];
-    lo = fminf(lo, v);
-    hi = fmaxf(hi, v);
-  }
-  lo = block_min(lo, sh);
-  hi = block_max(hi, sh);
-  if (threadIdx.x == 0) {
-    rmin[blockIdx.x] = lo;
-    rmax[blockIdx.x] = hi;
-  }
-}
-
-struct Norm {  // numpy float32 semantics of forward_utils.py:241-248
-  float pmin, pmax, imin, imax;
-  int pnorm, inorm;
-};
 
 // One block: global min/max, normalisation flags, fused image scores.
 __global__ __launch_bounds__(MT) void image_scores_kernel(const float* __restrict__ rmin,
@@ -88,21 +42,14 @@ __global__ __launch_bounds__(MT) void image_scores_kernel(const float* __restric
   hi = block_max(hi, sh);
   ilo = block_min(ilo, sh);
   ihi = block_max(ihi, sh);
-  const bool pn = hi != 1.0f, in = ihi != 1.0f;
+  const bool pn = norm_wanted(hi), in = norm_wanted(ihi);
   if (threadIdx.x == 0) *nrm = Norm{lo, hi, ilo, ihi, pn, in};
   for (int i = threadIdx.x; i < n_img; i += MT) {
     // max over pixels of the normalised map == normalised row max: fl((x-a)/b) is monotone
-    const float pm = pn ? (rmax[i] - lo) / (hi - lo) : rmax[i];
-    const float is = in ? (img[i] - ilo) / (ihi - ilo) : img[i];
+    const float pm = pn ? norm_apply(rmax[i], lo, hi) : rmax[i];
+    const float is = in ? norm_apply(img[i], ilo, ihi) : img[i];
     fused[i] = medical ? pm : pm * 0.5f + is * 0.5f;
   }
-}
-
-// order-preserving uint32 image of a float (+0 and -0 map to the same key)
-__device__ __forceinline__ uint32_t ord_bits(float v) {
-  if (v == 0.0f) v = 0.0f;
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
 __global__ __launch_bounds__(MT) void make_keys_kernel(const float* __restrict__ p, const uint8_t* __restrict__ lab,
@@ -110,8 +57,7 @@ __global__ __launch_bounds__(MT) void make_keys_kernel(const float* __restrict__
                                                        uint64_t* __restrict__ keys) {
   const Norm z = *nrm;
   for (int64_t i = (int64_t)blockIdx.x * MT + threadIdx.x; i < n; i += (int64_t)gridDim.x * MT) {
-    float v = p[i];
-    if (z.pnorm) v = (v - z.pmin) / (z.pmax - z.pmin);
+    const float v = pixel_score(p[i], z);
     keys[i] = ((uint64_t)ord_bits(v) << 1) | (lab[i] != 0 ? 1u : 0u);
   }
 }
@@ -444,11 +390,6 @@ __global__ __launch_bounds__(MT) void f1_image_partial_kernel(const float* __res
       if (f1_before(sh[k], r)) r = sh[k];
     part[blockIdx.x] = r;
   }
-}
-
-// the inverse of ord_bits
-__device__ __forceinline__ float ord_value(uint32_t k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
 // out[5..8] = pixel F1-max, threshold, precision, recall (NaN where the pixel AUROC is NaN);

@@ -26,6 +26,9 @@
       are copied to the device; there is no CPU path (without a GPU it raises).
       pro=True adds the pixel AUPRO (aaclip_metrics_eval_pro), which the reference lacks;
       f1=True adds pixel and image F1-max and their thresholds (aaclip_metrics_eval_f1).
+  anomaly_regions            a threshold applied to a class's maps, as data (aaclip_extract_regions):
+      per image the 8-connected regions at or above it with area, bbox, centroid, peak and
+      ground-truth overlap. The reference's answer to "show me the defects" is visualize().
 FocalLoss / BinaryDiceLoss as classes with non-default arguments and visualize() (cv2)
 are out of scope.
 """
@@ -310,6 +313,45 @@ def metrics_eval_deferred(pixel_label, image_label, pixel_preds, image_preds, cl
     t = [x.to(dev, non_blocking=True) for x in t]
     res = ops.metrics_eval_device(t[0], t[1], t[2], t[3], medical=(domain == "Medical"), pro=pro, f1=f1)
     return _DeferredMetrics(res, class_names, pro, f1)
+
+
+def anomaly_regions(pixel_preds, threshold, pixel_label=None, *, normalise=True, min_area=1, max_regions=64):
+    """The defects of one class's maps as regions (aaclip_extract_regions): the 8-connected components
+    of the pixels whose score reaches `threshold`, per image. With normalise=True the score is the
+    class-normalised fp32 map value of metrics_eval, so the threshold may be the "pixel F1 threshold"
+    of metrics_eval_deferred(..., f1=True).values(); with normalise=False it is the raw map value.
+    Tensors or numpy arrays, [n, H, W] or [n, 1, H, W]; pixel_label (nonzero = anomalous) is optional.
+    Syncs and returns one entry per image:
+      {"n_regions": int, "regions": [{"label", "area", "bbox": [x0, y0, x1, y1], "centroid": [cx, cy],
+                                      "peak", "peak_xy": [x, y], "gt_area"}, ...]}
+    n_regions counts the regions of at least min_area pixels; "regions" holds the first max_regions of
+    them by area descending, then label ascending (label = 1 + the smallest linear index y * W + x of
+    the region; bbox inclusive; centroid in float64; peak the highest score and peak_xy the first pixel
+    in row-major order that reaches it; gt_area the region's pixels with pixel_label != 0, 0 without
+    one). There is no CPU path: without a GPU this raises."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("anomaly_regions runs on the MI355X kernels (aaclip_extract_regions); no GPU is visible "
+                           "and there is no CPU path")
+    dev = next((t.device for t in (pixel_preds, pixel_label) if isinstance(t, torch.Tensor) and t.is_cuda),
+               torch.device("cuda", torch.cuda.current_device()))
+    preds, lab = [x if x is None or isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+                  for x in (pixel_preds, pixel_label)]
+    preds = preds.to(dev, non_blocking=True)
+    lab = None if lab is None else lab.to(dev, non_blocking=True)
+    out = ops.extract_regions(preds, threshold, pixel_label=lab, normalise=normalise, min_area=min_area,
+                              max_regions=max_regions)
+    W = preds.shape[-1]
+    out = {k: v.cpu().tolist() for k, v in out.items()}  # (the first copy syncs)
+    images = []
+    for i, count in enumerate(out["n_regions"]):
+        if count == 0xFFFFFFFF:
+            raise RuntimeError(f"aaclip_extract_regions: the component labelling of image {i} hit its loop cap")
+        regions = [{"label": out["label"][i][j], "area": out["area"][i][j], "bbox": out["bbox"][i][j],
+                    "centroid": out["centroid"][i][j], "peak": out["peak"][i][j],
+                    "peak_xy": [out["peak_index"][i][j] % W, out["peak_index"][i][j] // W],
+                    "gt_area": out["gt_area"][i][j]} for j in range(min(count, int(max_regions)))]
+        images.append({"n_regions": count, "regions": regions})
+    return images
 
 
 def visualize(pixel_label, pixel_preds, file_names, save_dir, dataset_name, class_name):

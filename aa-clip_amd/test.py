@@ -34,7 +34,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from dataset import DOMAINS, get_dataset  # noqa: E402
-from forward_utils import get_adapted_text_embedding, metrics_eval_deferred, visualize  # noqa: E402
+from forward_utils import anomaly_regions, get_adapted_text_embedding, metrics_eval_deferred, visualize  # noqa: E402
 from model.adapter import AdaptedCLIP  # noqa: E402
 from model.clip import create_model  # noqa: E402
 from utils import setup_seed  # noqa: E402
@@ -161,7 +161,16 @@ def parse_args(argv=None):
     parser.add_argument("--f1", action="store_true",
                         help="add the pixel and image F1-max columns and log each class's operating points "
                              "(threshold, precision, recall; thresholds in the normalised score domains)")
-    return parser.parse_args(argv)
+    parser.add_argument("--regions", action="store_true",
+                        help="extract each class's defect regions at its pixel F1-max threshold (area, bbox, "
+                             "centroid, peak, ground-truth overlap per region; implies --f1)")
+    parser.add_argument("--regions_min_area", type=int, default=1, help="--regions: drop smaller regions")
+    parser.add_argument("--regions_max", type=int, default=64,
+                        help="--regions: regions listed per image, the largest first (all are counted)")
+    args = parser.parse_args(argv)
+    if args.regions:
+        args.f1 = True
+    return args
 
 
 def main(argv=None):
@@ -172,7 +181,8 @@ def run(args):
     """main() body; returns (results DataFrame, context dict with the model, the text
     anchors and every class's (masks, labels, preds, preds_image), with --f1 also
     "operating_points": per class the pixel and image F1-max threshold, precision and
-    recall) for callers/tests."""
+    recall, with --regions also "regions": per class {"threshold", "images": [{"file_name",
+    "n_regions", "regions"}]}, see forward_utils.anomaly_regions) for callers/tests."""
     setup_seed(args.seed)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -252,6 +262,8 @@ def run(args):
         ctx = {"model": model, "text_embeddings": text_embeddings, "classes": {}}
         if args.f1:
             ctx["operating_points"] = {}
+        if args.regions:
+            ctx["regions"], names = {}, {}
         for class_name, image_dataset in image_datasets.items():
             workers = 0 if synthetic else 4
             from dataset import collate_raw
@@ -278,6 +290,8 @@ def run(args):
             pending.append(metrics_eval_deferred(masks, labels, preds, preds_image, class_name,
                                                  domain=DOMAINS[args.dataset], pro=args.pro, f1=args.f1))
             ctx["classes"][class_name] = (masks, labels, preds, preds_image)
+            if args.regions:
+                names[class_name] = file_names
         for read in pending:
             row = read()
             df.loc[len(df)] = Series(row)
@@ -289,6 +303,21 @@ def run(args):
                 logger.info("%s F1-max operating points: %s", row["class name"], "; ".join(
                     "%s threshold %.6g, precision %.4f, recall %.4f" % (level, p["threshold"], p["precision"],
                                                                         p["recall"]) for level, p in op.items()))
+            if args.regions:
+                name, thr = row["class name"], op["pixel"]["threshold"]
+                if thr != thr:  # NaN: one pixel class only, no F1-max threshold
+                    logger.info("%s regions: no pixel F1-max threshold, none extracted", name)
+                    continue
+                masks, _, preds, _ = ctx["classes"][name]
+                found = anomaly_regions(preds, thr, masks, min_area=args.regions_min_area,
+                                        max_regions=args.regions_max)
+                ctx["regions"][name] = {"threshold": thr, "images": [dict(file_name=f, **r)
+                                                                     for f, r in zip(names[name], found)]}
+                logger.info("%s regions at pixel threshold %.6g: %d in %d of %d images, %d listed, %d of those "
+                            "overlap the ground truth", name, thr, sum(r["n_regions"] for r in found),
+                            sum(r["n_regions"] > 0 for r in found), len(found),
+                            sum(len(r["regions"]) for r in found),
+                            sum(g["gt_area"] > 0 for r in found for g in r["regions"]))
         if rank != 0:
             continue
         df.loc[len(df)] = df.drop(columns=["class name"]).mean()
@@ -301,6 +330,8 @@ def run(args):
                 table = {"world": world, "rows": df.astype({c: float for c in df.columns[1:]}).to_dict("records")}
                 if args.f1:
                     table["operating_points"] = ctx["operating_points"]
+                if args.regions:
+                    table["regions"] = ctx["regions"]
                 json.dump(table, f)
     return df, ctx
 

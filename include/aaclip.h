@@ -56,7 +56,9 @@ extern "C" {
  * aaclip_upsample_softmax_bwd, aaclip_patch_logits_bwd, aaclip_patch_logits_bwd_workspace)
  * was added under version 8: additions only, no existing signature changed. A version-8
  * library built before them is still refused by the loader, which checks that every
- * symbol it binds is exported ("lacks ...: stale"). */
+ * symbol it binds is exported ("lacks ...: stale"). The later additions under version 9
+ * (the device metrics' AUPRO and F1-max, aaclip_regions_workspace / aaclip_extract_regions)
+ * went in the same way. */
 int aaclip_abi_version(void);
 const char* aaclip_arch(void);
 
@@ -766,6 +768,47 @@ int aaclip_metrics_eval_f1(const float* pixel_preds, const uint8_t* pixel_label,
                            const uint8_t* image_label, int n_images, int height, int width, int medical,
                            int with_pro, double fpr_limit, void* workspace, size_t workspace_bytes, double* out13,
                            void* stream);
+
+/*
+ * The defect regions of one class's anomaly maps: the 8-connected components of the pixels whose
+ * score reaches a threshold, each with where it is, how large and how strong (what an inspection
+ * user does with the F1-max threshold of aaclip_metrics_eval_f1; the reference has no counterpart:
+ * its visualize() paints overlays with cv2).
+ * pixel_preds [n_images, height, width] fp32; pixel_label [same] uint8 (nonzero = anomalous) or NULL.
+ * Score v of a pixel: with normalise != 0 the class-normalised fp32 value of the metrics, bit for bit
+ * (lo / hi the fp32 min / max over all n_images maps; v = (x - lo) / (hi - lo) when hi != 1, else x:
+ * one shared formula, csrc/scorenorm.h), so that threshold may be out13[6] as it stands; with
+ * normalise == 0 v = x (serving: a raw threshold on the maps of VisualEngine.predict).
+ * A pixel is foreground when v >= threshold (the detection rule of the F1 kernels); a NaN v is
+ * background, so a constant class, which normalises to 0 / 0, has no region. Regions are the
+ * 8-connected components of the foreground per image, labelled by aaclip_label_components.
+ * Regions of area < min_area (>= 1) are dropped. n_regions [n_images] uint32: the regions that are
+ * left, which may exceed max_regions (>= 1); 0xFFFFFFFF where the labelling hit a cap (then the
+ * image's slots are zero). Every other output is [n_images, max_regions] slots; the first
+ * min(n_regions, max_regions) slots of an image hold its regions by area descending, ties by label
+ * ascending, the rest are zero:
+ *   labels        uint32  1 + the smallest linear index y * width + x of the region
+ *   areas         uint32  pixels
+ *   bboxes        uint32  [.., 4] = x0, y0, x1, y1, inclusive
+ *   centroids     double  [.., 2] = (double)sum x / (double)area, (double)sum y / (double)area: exact
+ *                         64-bit integer sums, one IEEE fp64 division each
+ *   peaks         float   the maximum v (a zero peak is +0)
+ *   peak_indices  uint32  the smallest linear index whose v is the peak
+ *   gt_areas      uint32  the region's pixels with pixel_label != 0 (0 with a NULL pixel_label)
+ * workspace: caller-owned device memory, 256-B aligned, of the size aaclip_regions_workspace reports
+ * for n_pixels = n_images * height * width (about 49 bytes per pixel: the labelling arrays and, for
+ * up to a component per two pixels, the per-region sums and sort buffers). Allocates nothing, does
+ * not sync. Integer atomics (min / max / add on 32- and 64-bit words; the peak and its index are one
+ * 64-bit max) and one radix sort: no floating-point atomics, the same bits on every launch. No loop
+ * depends on data beyond those of aaclip_label_components, which are capped. Needs
+ * height * width < 2^31, n_images * height * width < 2^32 - 1 and n_images * max_regions < 2^31.
+ */
+int aaclip_regions_workspace(int64_t n_pixels, int n_images, size_t* bytes);
+int aaclip_extract_regions(const float* pixel_preds, const uint8_t* pixel_label, int n_images, int height, int width,
+                           float threshold, int normalise, int min_area, int max_regions, void* workspace,
+                           size_t workspace_bytes, uint32_t* n_regions, uint32_t* labels, uint32_t* areas,
+                           uint32_t* bboxes, double* centroids, float* peaks, uint32_t* peak_indices,
+                           uint32_t* gt_areas, void* stream);
 
 /*
  * Test-time preprocessing (replaces dataset/__init__.py:127-143
