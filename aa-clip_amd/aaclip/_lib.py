@@ -97,6 +97,11 @@ SIGNATURES = {
     "aaclip_regions_workspace": [_L, _I, ctypes.POINTER(ctypes.c_size_t)],
     "aaclip_extract_regions": [_P, _P, _I, _I, _I, _F, _I, _I, _I, _P, ctypes.c_size_t, _P, _P, _P, _P, _P, _P, _P, _P,
                                _P],
+    "aaclip_bilinear_plan": [_I, _I, _P],
+    "aaclip_resize_bilinear_u8": [_P, _L, _L, _I, _I, _I, _P, _P, _I, _P, _P],
+    "aaclip_overlay_workspace": [_I, ctypes.POINTER(ctypes.c_size_t)],
+    "aaclip_overlay_range": [_P, _I, _L, _P, ctypes.c_size_t, _P, _P],
+    "aaclip_overlay_panels": [_P, _P, _P, _P, _I, _I, _I, _P, _P],
     "aaclip_bicubic_taps": [_I, _I, ctypes.POINTER(_I)],
     "aaclip_bicubic_plan": [_I, _I, _P, _P, _I],
     "aaclip_nearest_plan": [_I, _I, _P],

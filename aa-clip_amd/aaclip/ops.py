@@ -1430,6 +1430,103 @@ def extract_regions(pixel_preds, threshold, *, pixel_label=None, normalise=True,
         return out
 
 
+_bilinear_plans: dict = {}
+
+
+def bilinear_plan(in_size: int, out_size: int):
+    """The per-axis table of aaclip_resize_bilinear_u8: int32 [out_size, 3] = (s, a0, a1). Host only."""
+    import numpy as np
+    table = np.zeros((int(out_size), 3), np.int32)
+    call("aaclip_bilinear_plan", int(in_size), int(out_size), table.ctypes.data_as(ctypes.c_void_p))
+    return table
+
+
+def resize_bilinear_u8(src, size, out=None):
+    """8-bit fixed-point bilinear resize on the device (aaclip_resize_bilinear_u8, the resize of
+    forward_utils.visualize): src uint8 [B, h, w, 3] RGB (pixel rows contiguous; the row pitch and the
+    image stride may be padded) -> uint8 [B, size, size, 3]. The per-axis tables are built on the
+    host and cached per (source size, size, device)."""
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[-1] != 3 or src.numel() == 0:
+        raise ValueError(f"src must be a non-empty uint8 [B, h, w, 3], got {src.dtype} {tuple(src.shape)}")
+    if src.stride(3) != 1 or src.stride(2) != 3 or src.stride(1) < 3 * src.shape[2] or \
+            (src.shape[0] > 1 and src.stride(0) < src.stride(1) * src.shape[1]):
+        raise ValueError("pixel rows must be contiguous (the row pitch and the image stride may be padded)")
+    S = int(size)
+    if S < 1:
+        raise ValueError(f"size must be at least 1, got {size}")
+    if not src.is_cuda:
+        raise RuntimeError("aaclip ops need device (HIP) tensors; there is no CPU path")
+    B, h, w, _ = src.shape
+    if out is None:
+        out = torch.empty(B, S, S, 3, device=src.device, dtype=torch.uint8)
+    if tuple(out.shape) != (B, S, S, 3) or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 {(B, S, S, 3)}")
+    with torch.cuda.device(src.device):
+        _dev(src, out)
+        tables = []
+        for n in (w, h):
+            key = (n, S, src.device)
+            if key not in _bilinear_plans:
+                _bilinear_plans[key] = torch.from_numpy(bilinear_plan(n, S)).to(src.device)
+            tables.append(_bilinear_plans[key])
+        call("aaclip_resize_bilinear_u8", _ptr(src), src.stride(0), src.stride(1), B, h, w, _ptr(tables[0]),
+             _ptr(tables[1]), S, _ptr(out), _stream())
+    return out
+
+
+def overlay_range(maps):
+    """(lo, hi) of a class's maps as a device fp32 [2] (aaclip_overlay_range), without a host sync."""
+    if maps.dim() < 2 or maps.numel() == 0:
+        raise ValueError(f"maps must be a non-empty [n, ...], got {tuple(maps.shape)}")
+    maps = maps.to(torch.float32).contiguous()
+    n = maps.shape[0]
+    with torch.cuda.device(maps.device):
+        _dev(maps)
+        need = ctypes.c_size_t(0)
+        call("aaclip_overlay_workspace", n, ctypes.byref(need))
+        ws = torch.empty(int(need.value) // 4, device=maps.device, dtype=torch.float32)
+        out = torch.empty(2, device=maps.device, dtype=torch.float32)
+        call("aaclip_overlay_range", _ptr(maps), n, maps.numel() // n, _ptr(ws), need.value, _ptr(out), _stream())
+    return out
+
+
+def overlay_panels(maps, thumbs, *, labels=None, value_range=None, swap_rb=True, out=None):
+    """The three stacked panels of forward_utils.visualize (aaclip_overlay_panels): maps fp32
+    [n, S, S] or [n, 1, S, S]; thumbs uint8 [n, S, S, 3] RGB; labels the maps' shape (nonzero =
+    anomalous) or None; value_range a device fp32 [2] = (lo, hi) of the class (overlay_range) or
+    None for no normalisation; swap_rb exchanges the photo's red and blue as the reference's files
+    have them. Returns uint8 [n, 3 S, S, 3], enqueued without a host sync."""
+    if maps.dim() == 4 and maps.shape[1] == 1:
+        maps = maps[:, 0]
+    if maps.dim() != 3 or maps.numel() == 0 or maps.shape[1] != maps.shape[2]:
+        raise ValueError(f"maps must be a non-empty [n, S, S] or [n, 1, S, S], got {tuple(maps.shape)}")
+    maps = maps.to(torch.float32).contiguous()
+    n, S, _ = maps.shape
+    if thumbs.dtype != torch.uint8 or tuple(thumbs.shape) != (n, S, S, 3):
+        raise ValueError(f"thumbs must be uint8 {(n, S, S, 3)}, got {thumbs.dtype} {tuple(thumbs.shape)}")
+    thumbs = thumbs.contiguous()
+    lab = None
+    if labels is not None:
+        if labels.dim() == 4 and labels.shape[1] == 1:
+            labels = labels[:, 0]
+        if tuple(labels.shape) != (n, S, S):
+            raise ValueError(f"labels must match maps {(n, S, S)}, got {tuple(labels.shape)}")
+        lab = (labels != 0).to(torch.uint8).contiguous()
+    if value_range is not None:
+        if value_range.dtype != torch.float32 or tuple(value_range.shape) != (2,):
+            raise ValueError("value_range must be a device fp32 [2] = (lo, hi)")
+        value_range = value_range.contiguous()
+    if out is None:
+        out = torch.empty(n, 3 * S, S, 3, device=maps.device, dtype=torch.uint8)
+    if tuple(out.shape) != (n, 3 * S, S, 3) or out.dtype != torch.uint8 or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 {(n, 3 * S, S, 3)}")
+    with torch.cuda.device(maps.device):
+        _dev(maps, thumbs, lab, value_range, out)
+        call("aaclip_overlay_panels", _ptr(maps), _ptr(lab), _ptr(thumbs), _ptr(value_range), n, S, int(bool(swap_rb)),
+             _ptr(out), _stream())
+    return out
+
+
 def _metrics_eval_dev(preds, lab, ip, il, N, pix, medical):
     _dev(preds, lab, ip, il)
     need = ctypes.c_size_t(0)

@@ -47,13 +47,8 @@ __global__ __launch_bounds__(MT) void class_norm_kernel(const float* __restrict_
     if (threadIdx.x == 0) *nrm = Norm{0.f, 0.f, 0.f, 0.f, 0, 0};
     return;
   }
-  float lo = INFINITY, hi = -INFINITY;
-  for (int i = threadIdx.x; i < n_img; i += MT) {
-    lo = fminf(lo, rmin[i]);
-    hi = fmaxf(hi, rmax[i]);
-  }
-  lo = block_min(lo, sh);
-  hi = block_max(hi, sh);
+  float lo, hi;
+  class_minmax(rmin, rmax, n_img, sh, lo, hi);
   if (threadIdx.x == 0) *nrm = Norm{lo, hi, 0.f, 0.f, norm_wanted(hi), 0};
 }
 

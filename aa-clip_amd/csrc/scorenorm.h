@@ -49,6 +49,19 @@ __global__ __launch_bounds__(MT) void row_minmax_kernel(const float* __restrict_
   }
 }
 
+// the class's min / max from the per-image ones (whole block; every thread gets both)
+__device__ __forceinline__ void class_minmax(const float* __restrict__ rmin, const float* __restrict__ rmax,
+                                             int n_img, float* sh, float& lo, float& hi) {
+  lo = INFINITY;
+  hi = -INFINITY;
+  for (int i = threadIdx.x; i < n_img; i += MT) {
+    lo = fminf(lo, rmin[i]);
+    hi = fmaxf(hi, rmax[i]);
+  }
+  lo = block_min(lo, sh);
+  hi = block_max(hi, sh);
+}
+
 struct Norm {  // numpy float32 semantics of forward_utils.py:241-248
   float pmin, pmax, imin, imax;
   int pnorm, inorm;

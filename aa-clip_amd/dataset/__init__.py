@@ -210,6 +210,13 @@ class SyntheticSingleClassDataset(Dataset):
         return {"image": torch.from_numpy(img), "mask": torch.from_numpy(mask), "label": int(mask.max() > 0),
                 "file_name": f"synthetic/{idx:05d}.png", "class_name": self.class_name}
 
+    def source_u8(self, idx):
+        """Item idx as the photo it would have come from: the normalisation undone, uint8 RGB
+        [S, S, 3] (host numpy; values outside 0..255 are clipped). What visualize() is given for
+        the synthetic datasets, which have no files."""
+        img = self[idx]["image"].numpy()
+        return np.clip(np.rint((img * STD + MEAN) * 255.0), 0, 255).astype(np.uint8).transpose(1, 2, 0).copy()
+
 
 def collate_raw(items):
     """Batch raw items: uint8 images/masks stacked when the sizes agree (one

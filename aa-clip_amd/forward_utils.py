@@ -28,18 +28,25 @@
       f1=True adds pixel and image F1-max and their thresholds (aaclip_metrics_eval_f1).
   anomaly_regions            a threshold applied to a class's maps, as data (aaclip_extract_regions):
       per image the 8-connected regions at or above it with area, bbox, centroid, peak and
-      ground-truth overlap. The reference's answer to "show me the defects" is visualize().
-FocalLoss / BinaryDiceLoss as classes with non-default arguments and visualize() (cv2)
-are out of scope.
+      ground-truth overlap.
+  visualize                  forward_utils.py:283-327 without cv2 — the three-panel overlays (photo, ground
+      truth over photo, prediction over photo) rendered on the device: aaclip_resize_bilinear_u8
+      (8-bit fixed-point bilinear), aaclip_overlay_range, aaclip_overlay_panels (quantise, jet
+      ramp, integer blend, stack), encoded with Pillow on a small thread pool. The recipe is this
+      build's own statement of what the reference asks of cv2 (include/aaclip.h,
+      tests/visualize_ref.py); equality with an OpenCV build's bytes is not claimed.
+FocalLoss / BinaryDiceLoss as classes with non-default arguments are out of scope.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
 
 from aaclip import ops
 from aaclip.engine import _blur_for
-from dataset.constants import CLASS_NAMES, PROMPTS, REAL_NAMES
+from dataset.constants import CLASS_NAMES, DATA_PATH, PROMPTS, REAL_NAMES
 from model.tokenizer import tokenize
 
 prompt = PROMPTS
@@ -354,5 +361,111 @@ def anomaly_regions(pixel_preds, threshold, pixel_label=None, *, normalise=True,
     return images
 
 
-def visualize(pixel_label, pixel_preds, file_names, save_dir, dataset_name, class_name):
-    raise NotImplementedError("visualize() writes cv2 overlays; cv2 is not in this image and it is not on the path")
+_VIS_CHUNK = 32  # images rendered, copied and handed to the encoders at a time
+
+
+def visualization_path(save_dir, dataset_name, class_name, file_name):
+    """forward_utils.py:306, :316-317: save_dir/visualization/<dataset>/<class>/<damage>_<image name>,
+    from the last two components of the file name. The reference raises for every dataset but
+    MVTec; the same naming serves all of them here."""
+    damage_name, image_name = file_name.split("/")[-2:]
+    return os.path.join(save_dir, "visualization", dataset_name, class_name, f"{damage_name}_{image_name}")
+
+
+def _thumbnails(sources, S, dev):
+    """uint8 [h, w, 3] sources (numpy arrays or tensors) -> device uint8 [n, S, S, 3]: grouped by
+    size, one aaclip_resize_bilinear_u8 launch per size and chunk."""
+    srcs = [s if isinstance(s, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(s)) for s in sources]
+    for s in srcs:
+        if s.dtype != torch.uint8 or s.dim() != 3 or s.shape[2] != 3:
+            raise ValueError(f"images must be uint8 [h, w, 3], got {s.dtype} {tuple(s.shape)}")
+    out = torch.empty(len(srcs), S, S, 3, device=dev, dtype=torch.uint8)
+    by_size = {}
+    for i, s in enumerate(srcs):
+        by_size.setdefault(tuple(s.shape), []).append(i)
+    for idx in by_size.values():
+        for a in range(0, len(idx), _VIS_CHUNK):
+            part = idx[a:a + _VIS_CHUNK]
+            batch = torch.stack([srcs[i] for i in part]).to(dev, non_blocking=True)
+            out[torch.tensor(part, device=dev)] = ops.resize_bilinear_u8(batch, S)
+    return out
+
+
+def visualize(pixel_label, pixel_preds, file_names, save_dir, dataset_name, class_name, *, images=None,
+              true_color=False, workers=4):
+    """forward_utils.py:288-327 without cv2: per test image one picture of three panels stacked top
+    to bottom (the photo, the ground truth over it, the prediction over it), rendered on the device
+    (aaclip_resize_bilinear_u8, aaclip_overlay_range, aaclip_overlay_panels; the recipe is stated in
+    include/aaclip.h and restated in numpy by tests/visualize_ref.py) and written with Pillow to
+    visualization_path(...), at the source's extension. The first six arguments are the reference's;
+    labels [n, 1, S, S] or [n, S, S] and maps [n, S, S] or [n, 1, S, S] may be numpy arrays or device
+    tensors. images: the photos, as a list of uint8 [h, w, 3] RGB arrays or as a device uint8
+    [n, S, S, 3] tensor of thumbnails already resized; without it the files are read from
+    DATA_PATH[dataset_name] (Pillow, convert("RGB")). true_color=False keeps the reference's files,
+    whose photo has red and blue exchanged under a true-coloured ramp (it blends an RGB photo with a
+    BGR ramp and writes BGR); true_color=True writes the photo as it is. workers: encoder threads.
+    Returns the written paths. There is no CPU path: without a GPU this raises."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("visualize renders on the MI355X kernels (aaclip_overlay_panels); no GPU is visible "
+                           "and there is no CPU path")
+    from concurrent.futures import ThreadPoolExecutor
+
+    from PIL import Image
+    dev = next((t.device for t in (pixel_preds, pixel_label, images) if isinstance(t, torch.Tensor) and t.is_cuda),
+               torch.device("cuda", torch.cuda.current_device()))
+    preds, lab = [x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+                  for x in (pixel_preds, pixel_label)]
+    preds = preds.to(dev, non_blocking=True)
+    lab = lab.to(dev, non_blocking=True)
+    if preds.dim() == 4 and preds.shape[1] == 1:
+        preds = preds[:, 0]
+    if preds.dim() != 3 or preds.shape[1] != preds.shape[2]:
+        raise ValueError(f"pixel_preds must be [n, S, S] or [n, 1, S, S], got {tuple(preds.shape)}")
+    n, S, _ = preds.shape
+    if lab.numel() != preds.numel() or len(file_names) != n:
+        raise ValueError(f"{n} maps of {S} x {S} need as many labels and file names, got {tuple(lab.shape)} and "
+                         f"{len(file_names)}")
+    lab = lab.reshape(n, S, S)
+    paths = [visualization_path(save_dir, dataset_name, class_name, f) for f in file_names]
+    if n == 0:
+        return paths
+    os.makedirs(os.path.dirname(paths[0]), exist_ok=True)
+    preds = preds.to(torch.float32).contiguous()
+    workers = max(1, int(workers))
+
+    def load(file):
+        with Image.open(os.path.join(DATA_PATH[dataset_name], file)) as im:
+            return np.array(im.convert("RGB"))
+
+    def save(array, path):
+        Image.fromarray(array).save(path)
+
+    with torch.cuda.device(dev), ThreadPoolExecutor(max_workers=workers) as pool:
+        value_range = ops.overlay_range(preds)  # of the whole class, as the metrics take it
+        thumbs = None
+        if isinstance(images, torch.Tensor):
+            if images.dtype != torch.uint8 or tuple(images.shape) != (n, S, S, 3):
+                raise ValueError(f"a thumbnail tensor must be uint8 {(n, S, S, 3)}, got {tuple(images.shape)}")
+            thumbs = images.to(dev)
+        elif images is not None and len(images) != n:
+            raise ValueError(f"{n} maps need {n} images, got {len(images)}")
+        pinned = [torch.empty(min(n, _VIS_CHUNK), 3 * S, S, 3, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        busy = [[], []]  # the encodes still reading each pinned buffer
+        for k, a in enumerate(range(0, n, _VIS_CHUNK)):
+            b = min(a + _VIS_CHUNK, n)
+            if thumbs is not None:
+                part = thumbs[a:b]
+            else:
+                part = _thumbnails(list(pool.map(load, file_names[a:b])) if images is None else images[a:b], S, dev)
+            out = ops.overlay_panels(preds[a:b], part, labels=lab[a:b], value_range=value_range,
+                                     swap_rb=not true_color)
+            host = pinned[k % 2]
+            for f in busy[k % 2]:
+                f.result()
+            host[:b - a].copy_(out, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            busy[k % 2] = [pool.submit(save, host[i].numpy(), paths[a + i]) for i in range(b - a)]
+        for fs in busy:
+            for f in fs:
+                f.result()
+    return paths

@@ -18,7 +18,11 @@ Differences from the reference, all on the host side:
   * under torchrun (WORLD_SIZE > 1, one process per GPU) every class's test set is
     sharded by image (aaclip.parallel.shard_range), each rank predicts its shard and
     the maps / scores / masks / labels are gathered (RCCL) onto rank 0, which runs
-    metrics_eval and prints and logs the table.
+    metrics_eval and prints and logs the table;
+  * --visualize hands visualize() the device tensors: the overlays are rendered on the
+    device, from thumbnails made at batch time out of the photos already there (single
+    process, --gpu_preprocess), from the files otherwise (rank 0 in a sharded run), and
+    for the synthetic datasets from the items un-normalised (source_u8).
 """
 from __future__ import annotations
 
@@ -40,17 +44,26 @@ from model.clip import create_model  # noqa: E402
 from utils import setup_seed  # noqa: E402
 
 
-def _device_batch(input_data, prep, device):
+def _device_batch(input_data, prep, device, thumbs=None):
     """One loader batch -> (image fp32 [B,3,S,S], mask uint8 [B,1,S,S]) on the device:
     raw uint8 batches (dataset raw=True) go through aaclip_preprocess_images /
     aaclip_resize_masks_nearest, normalised ones are copied (non_blocking from the
-    DataLoader's pinned memory). Runs on the caller's current stream."""
+    DataLoader's pinned memory). Runs on the caller's current stream. thumbs (a list, raw
+    batches only): the batch's uint8 [B,S,S,3] thumbnails for visualize() are appended to it,
+    resized from the same device copy of the photos (aaclip_resize_bilinear_u8)."""
     if prep is not None:
-        def run(fn, u8):
+        def to_dev(u8):
             if isinstance(u8, torch.Tensor):
-                return fn(u8.to(device, non_blocking=True))
-            return torch.cat([fn(t.to(device, non_blocking=True)[None]) for t in u8])
-        image, mask = run(prep.images, input_data["image_u8"]), run(prep.masks, input_data["mask_u8"])
+                return u8.to(device, non_blocking=True)
+            return [t.to(device, non_blocking=True)[None] for t in u8]
+
+        def run(fn, u8):
+            return fn(u8) if isinstance(u8, torch.Tensor) else torch.cat([fn(t) for t in u8])
+        image_u8 = to_dev(input_data["image_u8"])
+        image, mask = run(prep.images, image_u8), run(prep.masks, to_dev(input_data["mask_u8"]))
+        if thumbs is not None:
+            from aaclip import ops
+            thumbs.append(run(lambda t: ops.resize_bilinear_u8(t, prep.S), image_u8))
     else:
         image = input_data["image"].to(device, non_blocking=True)
         mask = torch.as_tensor(input_data["mask"]).to(device, non_blocking=True)
@@ -58,7 +71,7 @@ def _device_batch(input_data, prep, device):
 
 
 def get_predictions(model, class_text_embeddings, test_loader, device, img_size, dataset="MVTec", prep=None,
-                    n_total=None, streams=1):
+                    n_total=None, streams=1, sources=None):
     """test.py:53-99. Batch k+1 is copied to the device (and preprocessed, with prep) on a
     copy stream while batch k runs; maps, scores and masks stay on the device (the
     reference syncs twice per batch, test.py:85,93). Returns (masks uint8 [N,1,S,S]
@@ -67,31 +80,41 @@ def get_predictions(model, class_text_embeddings, test_loader, device, img_size,
     of a class's n_total images) the class is gathered in shard order onto rank 0, which
     alone runs metrics_eval; the other ranks return None for the tensors. A rank with an
     empty shard still takes part. streams: concurrent image chunks per batch (HIP
-    streams) for batches of at least 8 images per chunk; results do not depend on it."""
+    streams) for batches of at least 8 images per chunk; results do not depend on it.
+    sources (a list; single-process raw mode, i.e. with prep and without n_total): each batch's
+    uint8 [B,S,S,3] thumbnails are appended to it, made at batch time from the photos already
+    on the device, so visualize() decodes nothing twice. Otherwise it is left empty."""
     masks, labels, preds, preds_image, file_names = [], [], [], [], []
     device = torch.device(device)
     on_gpu = device.type == "cuda"  # (a CPU device only in the host-logic tests, with a stand-in model)
     main = torch.cuda.current_stream(device) if on_gpu else None
     copy = torch.cuda.Stream(device=device) if on_gpu else None
 
+    want_thumbs = sources is not None and prep is not None and n_total is None
+
     def stage(batch):
+        thumbs = [] if want_thumbs else None
         if not on_gpu:
-            return (batch,) + _device_batch(batch, prep, device) + (None,)
+            return (batch,) + _device_batch(batch, prep, device, thumbs) + (None, thumbs)
         with torch.cuda.stream(copy):
-            image, mask = _device_batch(batch, prep, device)
+            image, mask = _device_batch(batch, prep, device, thumbs)
         ev = torch.cuda.Event()
         ev.record(copy)
-        return batch, image, mask, ev
+        return batch, image, mask, ev, thumbs
 
     it = iter(test_loader)
     first = next(it, None)
     staged = stage(first) if first is not None else None
     while staged is not None:
-        input_data, image, mask, ready = staged
+        input_data, image, mask, ready, thumbs = staged
         if on_gpu:
             main.wait_event(ready)
             image.record_stream(main)
             mask.record_stream(main)
+        if thumbs:
+            if on_gpu:
+                thumbs[0].record_stream(main)
+            sources.append(thumbs[0])
         class_name = input_data["class_name"]
         assert len(set(class_name)) == 1, "mixed class not supported"
         labels.append(np.asarray(input_data["label"]))
@@ -136,6 +159,9 @@ def parse_args(argv=None):
     parser.add_argument("--seed", type=int, default=111)
     parser.add_argument("--save_path", type=str, default="ckpt/baseline")
     parser.add_argument("--visualize", action="store_true")
+    parser.add_argument("--visualize_true_color", action="store_true",
+                        help="--visualize: write the photo in its true colours (the default keeps the reference's "
+                             "files, whose photo has red and blue exchanged under a true-coloured ramp)")
     parser.add_argument("--text_norm_weight", type=float, default=0.1)
     parser.add_argument("--text_adapt_weight", type=float, default=0.1)
     parser.add_argument("--image_adapt_weight", type=float, default=0.1)
@@ -267,7 +293,7 @@ def run(args):
         for class_name, image_dataset in image_datasets.items():
             workers = 0 if synthetic else 4
             from dataset import collate_raw
-            n_total = None
+            n_total, whole = None, image_dataset
             if world > 1:
                 from aaclip.parallel import shard_range
                 n_total = len(image_dataset)
@@ -276,16 +302,21 @@ def run(args):
             loader = torch.utils.data.DataLoader(image_dataset, batch_size=args.batch_size, shuffle=False,
                                                  num_workers=workers, pin_memory=True,
                                                  collate_fn=collate_raw if raw else None)
+            sources = [] if args.visualize else None
             with torch.no_grad():
                 masks, labels, preds, preds_image, file_names = get_predictions(
                     model=model, class_text_embeddings=text_embeddings[class_name], test_loader=loader,
                     device=device, img_size=args.img_size, dataset=args.dataset, prep=prep, n_total=n_total,
-                    streams=args.streams)
+                    streams=args.streams, sources=sources)
             if rank != 0:  # the class was gathered onto rank 0, which runs metrics_eval
                 continue
             if args.visualize:
-                visualize(masks.cpu().numpy(), preds.cpu().numpy(), file_names, args.save_path, args.dataset,
-                          class_name=class_name)
+                if synthetic:  # no files: the photos are the items, un-normalised on the host
+                    photos = [whole.source_u8(i) for i in range(len(whole))]
+                else:  # the batches' thumbnails; a sharded or Pillow-transform run reads the files
+                    photos = torch.cat(sources) if sources else None
+                visualize(masks, preds, file_names, args.save_path, args.dataset, class_name=class_name,
+                          images=photos, true_color=args.visualize_true_color)
             # enqueued now, read after the loop: the next class's batches start at once
             pending.append(metrics_eval_deferred(masks, labels, preds, preds_image, class_name,
                                                  domain=DOMAINS[args.dataset], pro=args.pro, f1=args.f1))

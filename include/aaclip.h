@@ -57,8 +57,8 @@ extern "C" {
  * was added under version 8: additions only, no existing signature changed. A version-8
  * library built before them is still refused by the loader, which checks that every
  * symbol it binds is exported ("lacks ...: stale"). The later additions under version 9
- * (the device metrics' AUPRO and F1-max, aaclip_regions_workspace / aaclip_extract_regions)
- * went in the same way. */
+ * (the device metrics' AUPRO and F1-max, aaclip_regions_workspace / aaclip_extract_regions, the
+ * overlay entry points of csrc/overlay.hip) went in the same way. */
 int aaclip_abi_version(void);
 const char* aaclip_arch(void);
 
@@ -809,6 +809,67 @@ int aaclip_extract_regions(const float* pixel_preds, const uint8_t* pixel_label,
                            size_t workspace_bytes, uint32_t* n_regions, uint32_t* labels, uint32_t* areas,
                            uint32_t* bboxes, double* centroids, float* peaks, uint32_t* peak_indices,
                            uint32_t* gt_areas, void* stream);
+
+/*
+ * Anomaly overlays (csrc/overlay.hip; replaces forward_utils.py:283-327, visualize() and
+ * apply_ad_scoremap(), which paint them with cv2 on the host). For one class: n maps fp32 [S, S],
+ * n labels [S, S], n photos resized to [S, S, 3] -> n images uint8 [3 S, S, 3], three panels stacked
+ * top to bottom: the photo, the ground truth over it, the prediction over it. Integer and fp32
+ * arithmetic with one stated result, restated in numpy by tests/visualize_ref.py, which the device
+ * equals byte for byte. cv2 itself is on no machine this was built on: the recipe is modelled on
+ * OpenCV's, and equality with an OpenCV build's bytes is not claimed.
+ *
+ * aaclip_bilinear_plan (host only; the table of cv2.resize's INTER_LINEAR 8-bit path, :312): for
+ * every output coordinate d of one axis table[3 d ..] = (s, a0, a1). With scale = in / out in double:
+ *   f = (float)((d + 0.5) * scale - 0.5);  s = floor(f);  f -= s;
+ *   s < 0: s = 0, f = 0;   s >= in - 1: s = in - 1, f = 0;
+ *   a1 = rint(f * 2048), a0 = rint((1 - f) * 2048), both in fp32 (a0 + a1 = 2048).
+ *
+ * aaclip_resize_bilinear_u8: src batch uint8 RGB [in_h, in_w, 3] (row pitch / image stride in
+ * bytes), x_table / y_table device copies of the plans of (in_w, S) / (in_h, S), out uint8
+ * [batch, S, S, 3]. With the neighbour index min(s + 1, in - 1), per channel in int:
+ *   r(row) = src[row][sx] * a0 + src[row][sx + 1] * a1                       (horizontal)
+ *   dst = (((b0 * (r(sy) >> 4)) >> 16) + ((b1 * (r(sy + 1) >> 4)) >> 16) + 2) >> 2   (vertical)
+ * in == out is the identity. A table index outside the source is clamped into it. Needs
+ * batch * S * S < 2^31 - 4.
+ *
+ * aaclip_overlay_range (:296-299): range[0] = lo, range[1] = hi, the fp32 min / max over the
+ * class's maps [n_images, pix_per_image] (NaNs are skipped, as fminf / fmaxf do), into a device
+ * float[2]. workspace: caller-owned device memory of aaclip_overlay_workspace bytes (the partial
+ * minima and maxima: an image is reduced in up to 64 equal parts). Min / max only and no atomics:
+ * the same bits on every launch. Needs n_images <= 2^24.
+ *
+ * aaclip_overlay_panels (:296-303, :283-285, :321-326): maps fp32 [batch, S, S]; labels uint8
+ * [batch, S, S] or NULL (all zero); thumbs uint8 [batch, S, S, 3] RGB (aaclip_resize_bilinear_u8);
+ * range a device float[2] or NULL (no normalisation); out uint8 [batch, 3 S, S, 3].
+ *   q  v = the class-normalised score of csrc/scorenorm.h: (x - lo) / (hi - lo) when hi != 1, else
+ *      x (also with a NULL range); q = (uint8)trunc(v * 255.0f) in fp32, numpy's
+ *      (pixel_preds * 255).astype(np.uint8). Defined here where the reference is not: a non-finite
+ *      v (a constant class is 0 / 0) gives q = 0, and a finite v outside [0, 1] (hi == 1, where
+ *      the reference hands floats to cv2) is clamped to 0..255 after the truncation.
+ *   L  255 where the label != 0, else 0.
+ *   JET(u), u in 0..255, RGB: r = clip(383 - |4 u - 765|, 0, 255), g the same around 510, b around
+ *      255: JET(0) = (0, 0, 128), JET(255) = (128, 0, 0).
+ *   P  the photo with red and blue exchanged when swap_rb != 0, else the photo. The reference
+ *      blends an RGB photo with applyColorMap's BGR ramp and writes the sum as BGR, so on disk its
+ *      photo has red and blue swapped and the ramp has its true colours: swap_rb = 1 is that.
+ *   panel 0 = P, panel 1 = (P + JET(L)) >> 1, panel 2 = (P + JET(q)) >> 1 per channel in int,
+ *   which is (0.5 * a + 0.5 * b).astype(uint8) exactly; out is in file (true RGB) channel order.
+ * One pass, each input read once, 16-byte stores except at the ends of a block's runs.
+ * Needs batch <= 65535 and S <= 16384.
+ *
+ * All of them allocate nothing, do not sync and return AACLIP_ERR_ARG for NULL or non-positive
+ * arguments.
+ */
+int aaclip_bilinear_plan(int in_size, int out_size, int32_t* table);
+int aaclip_resize_bilinear_u8(const uint8_t* src, int64_t img_stride, int64_t row_pitch, int batch, int in_h,
+                              int in_w, const int32_t* x_table, const int32_t* y_table, int out_size, uint8_t* out,
+                              void* stream);
+int aaclip_overlay_workspace(int n_images, size_t* bytes);
+int aaclip_overlay_range(const float* maps, int n_images, int64_t pix_per_image, void* workspace,
+                         size_t workspace_bytes, float* range, void* stream);
+int aaclip_overlay_panels(const float* maps, const uint8_t* labels, const uint8_t* thumbs, const float* range,
+                          int batch, int size, int swap_rb, uint8_t* out, void* stream);
 
 /*
  * Test-time preprocessing (replaces dataset/__init__.py:127-143
