@@ -952,41 +952,60 @@ def linear_wgrad(dy, x, *, out=None, workspace=None):
 
 
 # ------------------------------------------------------------------------ stage-2 backward
-def attention_bwd_tiled_workspace(batch: int, seq: int, heads: int, device) -> torch.Tensor:
+def _attention_bwd_workspace(entry: str, batch: int, seq: int, heads: int, device) -> torch.Tensor:
     nbytes = ctypes.c_size_t(0)
-    call("aaclip_attention_bwd_tiled_workspace", batch, seq, heads, ctypes.byref(nbytes))
+    call(f"aaclip_{entry}_workspace", batch, seq, heads, ctypes.byref(nbytes))
     return torch.empty(int(nbytes.value) // 4, device=device, dtype=torch.float32)
+
+
+def _attention_bwd(entry: str, dtype, lead: tuple, flags: tuple, qkv, out, dout, batch: int, seq: int, heads: int,
+                   dqkv, workspace):
+    """The tiled attention backward behind attention_bwd_tiled (fp32) and attention_bwd16 (bf16):
+    `dtype` is the operands' element type, `lead` / `flags` the entry's arguments before qkv /
+    after head_dim."""
+    def check(t, name, shape):
+        if dtype == torch.float32:
+            _f32c(t, name, shape)
+        else:
+            _c16(t, name, dtype, shape)
+
+    hd = 64
+    if batch < 1 or heads < 1 or seq < 1:
+        raise ValueError(f"{entry} needs batch, heads and seq >= 1")
+    if batch * heads > 65535:
+        raise ValueError(f"{entry}: batch * heads must be <= 65535")
+    check(qkv, "qkv", (batch * seq, 3 * heads * hd))
+    check(out, "out", (batch * seq, heads * hd))
+    check(dout, "dout", (batch * seq, heads * hd))
+    if dqkv is None:
+        dqkv = torch.empty_like(qkv)
+    check(dqkv, "dqkv", qkv.shape)
+    if dqkv.data_ptr() in (qkv.data_ptr(), out.data_ptr(), dout.data_ptr()):
+        raise ValueError(f"{entry}: dqkv must not alias qkv, out or dout")
+    if workspace is None:
+        workspace = _attention_bwd_workspace(entry, batch, seq, heads, qkv.device)
+    if workspace.dtype != torch.float32 or not workspace.is_contiguous():
+        raise ValueError(f"{entry} workspace must be contiguous fp32")
+    for t in (qkv, out, dout, dqkv, workspace):
+        if t.data_ptr() % 16:
+            raise ValueError(f"{entry} operands must be 16-byte aligned")
+    _dev(qkv, out, dout, dqkv, workspace)  # after the shape / dtype checks: those need no device
+    # 2 launches: S twice + dP + dQ, and S + dP + dV + dK: 16 seq^2 hd FLOPs per (image, head)
+    _launch("visual_bwd", entry, 16.0 * batch * heads * seq * seq * hd,
+            (3 * qkv.numel() + 3 * dout.numel()) * qkv.element_size(), f"aaclip_{entry}", *lead, _ptr(qkv), _ptr(out),
+            _ptr(dout), _ptr(dqkv), batch, seq, heads, hd, *flags, _ptr(workspace), workspace.numel() * 4, _stream())
+    return dqkv
+
+
+def attention_bwd_tiled_workspace(batch: int, seq: int, heads: int, device) -> torch.Tensor:
+    return _attention_bwd_workspace("attention_bwd_tiled", batch, seq, heads, device)
 
 
 def attention_bwd_tiled(qkv, out, dout, batch: int, seq: int, heads: int, *, dqkv=None, workspace=None):
     """dqkv [batch*seq, 3*heads*64] of the fp32 non-causal attention core, any seq >= 1, from
     the packed qkv, the forward's output out and dout (both [batch*seq, heads*64])."""
-    hd = 64
-    if batch < 1 or heads < 1 or seq < 1:
-        raise ValueError("attention_bwd_tiled needs batch, heads and seq >= 1")
-    if batch * heads > 65535:
-        raise ValueError("attention_bwd_tiled: batch * heads must be <= 65535")
-    _f32c(qkv, "qkv", (batch * seq, 3 * heads * hd))
-    _f32c(out, "out", (batch * seq, heads * hd))
-    _f32c(dout, "dout", (batch * seq, heads * hd))
-    if dqkv is None:
-        dqkv = torch.empty_like(qkv)
-    _f32c(dqkv, "dqkv", qkv.shape)
-    if dqkv.data_ptr() in (qkv.data_ptr(), out.data_ptr(), dout.data_ptr()):
-        raise ValueError("attention_bwd_tiled: dqkv must not alias qkv, out or dout")
-    if workspace is None:
-        workspace = attention_bwd_tiled_workspace(batch, seq, heads, qkv.device)
-    if workspace.dtype != torch.float32 or not workspace.is_contiguous():
-        raise ValueError("attention_bwd_tiled workspace must be contiguous fp32")
-    for t in (qkv, out, dout, dqkv, workspace):
-        if t.data_ptr() % 16:
-            raise ValueError("attention_bwd_tiled operands must be 16-byte aligned")
-    _dev(qkv, out, dout, dqkv, workspace)  # after the shape / dtype checks: those need no device
-    # 2 launches: S twice + dP + dQ, and S + dP + dV + dK: 16 seq^2 hd FLOPs per (image, head)
-    _launch("visual_bwd", "attention_bwd_tiled", 16.0 * batch * heads * seq * seq * hd,
-            (3 * qkv.numel() + 3 * dout.numel()) * 4, "aaclip_attention_bwd_tiled", _ptr(qkv), _ptr(out), _ptr(dout),
-            _ptr(dqkv), batch, seq, heads, hd, _ptr(workspace), workspace.numel() * 4, _stream())
-    return dqkv
+    return _attention_bwd("attention_bwd_tiled", torch.float32, (), (), qkv, out, dout, batch, seq, heads, dqkv,
+                          workspace)
 
 
 def tap_ln_bwd(dtap, x, w, g, batch: int, n_tok: int):
@@ -1045,9 +1064,7 @@ def _c16(t, name, dtype, shape=None):
 
 
 def attention_bwd16_workspace(batch: int, seq: int, heads: int, device) -> torch.Tensor:
-    nbytes = ctypes.c_size_t(0)
-    call("aaclip_attention_bwd16_workspace", batch, seq, heads, ctypes.byref(nbytes))
-    return torch.empty(int(nbytes.value) // 4, device=device, dtype=torch.float32)
+    return _attention_bwd_workspace("attention_bwd16", batch, seq, heads, device)
 
 
 def attention_bwd16(qkv, out, dout, batch: int, seq: int, heads: int, *, q_prescaled: bool = False, dqkv=None,
@@ -1056,34 +1073,9 @@ def attention_bwd16(qkv, out, dout, batch: int, seq: int, heads: int, *, q_presc
     the packed bf16 qkv, the forward's bf16 output out and bf16 dout (both [batch*seq, heads*64]).
     q_prescaled: the q columns carry log2(e)/sqrt(64) (ops.attention's flag); the q columns of
     dqkv are then the gradient of that prescaled q."""
-    hd = 64
-    if batch < 1 or heads < 1 or seq < 1:
-        raise ValueError("attention_bwd16 needs batch, heads and seq >= 1")
-    if batch * heads > 65535:
-        raise ValueError("attention_bwd16: batch * heads must be <= 65535")
-    bf = torch.bfloat16
-    _c16(qkv, "qkv", bf, (batch * seq, 3 * heads * hd))
-    _c16(out, "out", bf, (batch * seq, heads * hd))
-    _c16(dout, "dout", bf, (batch * seq, heads * hd))
-    if dqkv is None:
-        dqkv = torch.empty_like(qkv)
-    _c16(dqkv, "dqkv", bf, qkv.shape)
-    if dqkv.data_ptr() in (qkv.data_ptr(), out.data_ptr(), dout.data_ptr()):
-        raise ValueError("attention_bwd16: dqkv must not alias qkv, out or dout")
-    if workspace is None:
-        workspace = attention_bwd16_workspace(batch, seq, heads, qkv.device)
-    if workspace.dtype != torch.float32 or not workspace.is_contiguous():
-        raise ValueError("attention_bwd16 workspace must be contiguous fp32")
-    for t in (qkv, out, dout, dqkv, workspace):
-        if t.data_ptr() % 16:
-            raise ValueError("attention_bwd16 operands must be 16-byte aligned")
-    _dev(qkv, out, dout, dqkv, workspace)  # after the shape / dtype checks: those need no device
-    # 2 launches: S twice + dP + dQ, and S + dP + dV + dK: 16 seq^2 hd FLOPs per (image, head)
-    _launch("visual_bwd", "attention_bwd16", 16.0 * batch * heads * seq * seq * hd,
-            (3 * qkv.numel() + 3 * dout.numel()) * 2, "aaclip_attention_bwd16", _lib.BF16, _ptr(qkv), _ptr(out),
-            _ptr(dout), _ptr(dqkv), batch, seq, heads, hd, _lib.ATTN_Q_PRESCALED if q_prescaled else 0,
-            _ptr(workspace), workspace.numel() * 4, _stream())
-    return dqkv
+    return _attention_bwd("attention_bwd16", torch.bfloat16, (_lib.BF16,),
+                          (_lib.ATTN_Q_PRESCALED if q_prescaled else 0,), qkv, out, dout, batch, seq, heads, dqkv,
+                          workspace)
 
 
 def act_to16(x, mode, *, out):

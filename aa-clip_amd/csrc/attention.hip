@@ -17,19 +17,12 @@
 //   * online softmax in the log2 domain (v_exp_f32), fp32 statistics.
 #include <math.h>
 
-#include "common.h"
+#include "attn_lds.h"  // tr_read, swz, kAttnLog2Scale
 
 namespace {
 
 constexpr int HD_ = 64;      // head dim
 constexpr int KT = 64;       // keys per tile
-
-__device__ __forceinline__ short4_t tr_read(const char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) short4_t*)(p));
-}
-
-// byte offset of (row, 16-B chunk) in a swizzled [64][128 B] tile
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
 
 // Cross-lane max over the 4 lanes {c, c+16, c+32, c+48} that hold one query's
 // scores: v_permlane16_swap / v_permlane32_swap (VALU, no LDS round trip). The two
@@ -348,13 +341,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? ATTN_OCC : 4) void attn_bf16_ker
     for (int ks = 0; ks < 2; ++ks) qf[qb][ks] = *(const V8*)(base + (size_t)q * ld + ks * 32 + 8 * g);
   }
   if (!(flags & AACLIP_ATTN_Q_PRESCALED)) {  // log2(e)/sqrt(64) not folded by the caller: apply it here
-    constexpr float sl2 = 0.125f * 1.4426950408889634f;
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb)
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) qf[qb][ks][e] = (E)((float)qf[qb][ks][e] * sl2);
+        for (int e = 0; e < 8; ++e) qf[qb][ks][e] = (E)((float)qf[qb][ks][e] * kAttnLog2Scale);
   }
 
   // ---- DMA sources: wave w loads pieces i*4+w (8 rows each) of the K and V tiles
@@ -610,13 +602,12 @@ __global__ __launch_bounds__(256, 2) void attn_f32_kernel(const float* __restric
   const int q0 = blockIdx.x * 128 + wid * 32;
   const bool active = q0 < N;
 
-  constexpr float qscale = 0.125f * 1.4426950408889634f;  // 1/sqrt(64) * log2(e)
   float qv[QB][16];  // Q[q][4s + fq] for this lane's query q = q0 + 16 qb + fr
 #pragma unroll
   for (int qb = 0; qb < QB; ++qb) {
     const float* qr = base + (size_t)min(q0 + qb * 16 + fr, N - 1) * ld;
 #pragma unroll
-    for (int s4 = 0; s4 < 16; ++s4) qv[qb][s4] = qr[4 * s4 + fq] * qscale;
+    for (int s4 = 0; s4 < 16; ++s4) qv[qb][s4] = qr[4 * s4 + fq] * kAttnLog2Scale;
   }
 
   int ntiles = (N + KT - 1) / KT;

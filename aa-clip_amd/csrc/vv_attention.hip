@@ -19,14 +19,13 @@
 // token's result does not depend on which other tokens the launch holds.
 // Per layer the kernel reads and writes R x heads*64 elements once and does 6*B^2*64
 // fp32 FLOP per (token, head) (the recomputed pass included): bandwidth-bound at B = 16.
-#include "common.h"
+#include "attn_lds.h"  // kAttnLog2Scale
 
 namespace {
 
 constexpr int HD_ = 64;
 constexpr int VV_LDR = 68;    // LDS row stride in floats
 constexpr int VV_WAVES = 4;   // heads per workgroup
-constexpr float VV_LOG2_SCALE = 0.125f * 1.4426950408889634f;  // 1/sqrt(64) * log2(e)
 
 template <int DT>
 struct VvElem {  // 16-bit storage: 8 elements per 128-bit access
@@ -144,7 +143,7 @@ __global__ __launch_bounds__(64 * VV_WAVES) void vv_attention_kernel(
       // the maximum is taken on the raw scores and the scale applied to the difference: the
       // maximum's own argument is an exact 0 (a scaled score minus a scaled maximum could be
       // contracted into one fma and leave the product's rounding error there instead)
-      const float p = exp2f((vv_score<BP>(vb, vc) - m) * VV_LOG2_SCALE);
+      const float p = exp2f((vv_score<BP>(vb, vc) - m) * kAttnLog2Scale);
       l += p;
 #pragma unroll
       for (int j = 0; j < BP; ++j) acc[j] = fmaf(p, vc[j], acc[j]);

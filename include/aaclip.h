@@ -545,8 +545,8 @@ int aaclip_linear_wgrad(const float* dY, int64_t lddy, const float* X, int64_t l
                         float* workspace, size_t workspace_bytes, float* dW, int64_t lddw, void* stream);
 
 /* ------------------------------------------------------------------ stage-2 backward
- * Backward of the adapted visual tower (visual_bwd.hip; train.py:117-174 trains image_adapter
- * only). fp32, deterministic (no floating-point atomics, fixed reduction orders), image / row
+ * Backward of the adapted visual tower (attention_bwd.hip, visual_bwd.hip; train.py:117-174
+ * trains image_adapter only). fp32, deterministic (no floating-point atomics, fixed reduction orders), image / row
  * local; arguments are checked before the first launch, nothing allocates, synchronises or
  * reads on the host. The rest of the stage-2 backward is aaclip_layernorm_bwd, aaclip_act /
  * aaclip_act_bwd, aaclip_adapter_blend_bwd, aaclip_linear_wgrad and aaclip_gemm on transposed
@@ -602,7 +602,8 @@ int aaclip_l2_normalize_bwd(const float* dy, int64_t lddy, int dy_group, float s
                             float* dx, int64_t lddx, int rows, int width, void* stream);
 
 /* ------------------------------------------------------------------ stage-2 backward, bf16
- * The kernels of the bf16 mixed-precision stage-2 step (visual_bwd16.hip). The residual and
+ * The kernels of the bf16 mixed-precision stage-2 step (attention_bwd.hip's bf16
+ * instantiation, visual_bwd16.hip). The residual and
  * gradient streams, the LayerNorm / blend / normalise backwards and the weight gradients stay
  * the fp32 entries above; every GEMM is aaclip_gemm in bf16 on the transposed packed weights.
  *
