@@ -112,6 +112,10 @@ SIGNATURES = {
     "aaclip_color_jitter_workspace": [_I, ctypes.POINTER(ctypes.c_size_t)],
     "aaclip_color_jitter_u8": [_P, _L, _L, _I, _I, _I, _P, _P, _P, ctypes.c_size_t, _P],
     "aaclip_geom_augment": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "aaclip_bank_nn_workspace": [_I, _I, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(_I)],
+    "aaclip_bank_nn": [_I, _I, _I, _I, _P, _L, _P, _L, _P, ctypes.c_size_t, _P],
+    "aaclip_bank_distance": [_P, _I, _I, _I, _P, _P],
+    "aaclip_fewshot_fuse": [_P, _P, _P, _I, _L, _P, ctypes.c_size_t, _P, _P, _P, _P],
 }
 
 _lib = None

@@ -254,6 +254,19 @@ def _block_bwd(g, blk: dict, bt: dict, sv: dict, attend_bwd, act_mode: str, d_qk
     ops.layernorm_bwd(d_w, sv["x_in"], blk["ln1"][0], residual=g, out=g)   # 8. g_in
 
 
+class MemoryBank:
+    """The few-shot memory bank of one class (VisualEngine.build_bank): levels, a list of L device
+    tensors [shots * P, 768] of unit patch rows; img_size and dtype, which a predict_few_shot call
+    must match; shots, the number of support images."""
+
+    def __init__(self, levels: list, img_size: int, dtype: torch.dtype, shots: int):
+        self.levels, self.img_size, self.dtype, self.shots = list(levels), int(img_size), dtype, int(shots)
+
+    def __repr__(self):
+        return (f"MemoryBank(levels={len(self.levels)}, rows={self.levels[0].shape[0] if self.levels else 0}, "
+                f"img_size={self.img_size}, dtype={self.dtype}, shots={self.shots})")
+
+
 class VisualEngine:
     def __init__(self, vparams: dict, adapter: dict, *, levels=(6, 12, 18, 24), image_adapt_until=6,
                  image_adapt_weight=0.1, dtype=torch.bfloat16, fold_q_scale=True, fp8_scope="mlp",
@@ -820,6 +833,74 @@ class VisualEngine:
             ev.record(st)
             main.wait_event(ev)
         return out_map, out_score
+
+    # ------------------------------------------------------------------ few-shot memory bank
+    @property
+    def search_dtype(self):
+        """Operand dtype of the nearest-patch search: fp16 in every 16-bit and fp8 mode (unit rows fit
+        its range, three more mantissa bits than bf16 at the same MFMA rate), fp32 in the fp32 mode."""
+        return torch.float32 if self.dtype == torch.float32 else torch.float16
+
+    def _unit_rows(self, seg_raw):
+        out = []
+        for s_ in seg_raw:
+            y = torch.empty(s_.shape[0], EMBED, device=self.device, dtype=self.search_dtype)
+            out.append(ops.l2_normalize(s_, y))
+        return out
+
+    @torch.no_grad()
+    @_on_device
+    def bank_rows(self, x: torch.Tensor):
+        """The level features of x as unit rows: list[L] of [B*P, 768] in search_dtype (fresh tensors).
+        forward_raw without T, then aaclip_l2_normalize straight into that dtype."""
+        B, S = x.shape[0], x.shape[-1]
+        mc = self.max_chunk(S)
+        parts = [self._unit_rows(self.forward_raw(x[b0:min(B, b0 + mc)])[0]) for b0 in range(0, B, mc)]
+        return parts[0] if len(parts) == 1 else [torch.cat(lv) for lv in zip(*parts)]
+
+    def build_bank(self, support_images: torch.Tensor) -> "MemoryBank":
+        """The memory bank of k normal support images [k, 3, S, S] (reference test.py:39-50,
+        get_support_features): per level the k*P unit patch rows, in search_dtype."""
+        _check_image(support_images)
+        if support_images.shape[0] < 1:
+            raise ValueError("build_bank needs at least one support image")
+        return MemoryBank(self.bank_rows(support_images), int(support_images.shape[-1]), self.search_dtype,
+                          int(support_images.shape[0]))
+
+    @torch.no_grad()
+    @_on_device
+    def predict_few_shot(self, x: torch.Tensor, T: torch.Tensor, bank: "MemoryBank", domain: str = "Industrial"):
+        """Zero-shot and few-shot results of one batch: (zs_map [B,S,S], zs_score [B], fs_map [B,S,S]),
+        fp32, fresh tensors. zs_map / zs_score are predict()'s quantities from the projected rows (the
+        row path of _tail: the few-shot search needs the rows, so not the partials form). fs_map: per
+        level each patch's 1 - max cosine against the bank's rows of that level (ops.bank_nn +
+        ops.bank_distance), summed over the levels, then the domain's blur + upsample. Eager, on the
+        current stream."""
+        _check_image(x)
+        B, S = x.shape[0], x.shape[-1]
+        if not isinstance(bank, MemoryBank) or len(bank.levels) != len(self.levels):
+            raise ValueError(f"bank must be a MemoryBank of {len(self.levels)} levels (build_bank)")
+        if bank.img_size != S or bank.dtype != self.search_dtype:
+            raise ValueError(f"the bank was built at {bank.img_size} px in {bank.dtype}; this call is at {S} px in "
+                             f"{self.search_dtype}: rebuild it (build_bank)")
+        T = T.to(self.device, torch.float32).contiguous()
+        k, s = _blur_for(domain)
+        zs_map = torch.empty(B, S, S, device=self.device, dtype=torch.float32)
+        zs_score = torch.empty(B, device=self.device, dtype=torch.float32)
+        fs_map = torch.empty(B, S, S, device=self.device, dtype=torch.float32)
+        mc = self.max_chunk(S)
+        for b0 in range(0, B, mc):
+            b1 = min(B, b0 + mc)
+            seg_raw, det_raw, ws = self.forward_raw(x[b0:b1])
+            self._tail(seg_raw, det_raw, ws, T, zs_map[b0:b1], zs_score[b0:b1], k, s)
+            g = ws["g"]
+            grid = torch.empty(b1 - b0, 1, g, g, device=self.device, dtype=torch.float32)
+            part = None
+            for j, (q, r) in enumerate(zip(self._unit_rows(seg_raw), bank.levels)):
+                part = ops.bank_nn(q, r, part)
+                ops.bank_distance(part, grid, accumulate=j > 0)
+            ops.blur_upsample(grid, fs_map[b0:b1].view(b1 - b0, 1, S, S), ksize=k, sigma=s)
+        return zs_map, zs_score, fs_map
 
     GRAPH_CACHE = 4  # captured steps kept per engine (predict_cached), least recently used dropped
 

@@ -1529,3 +1529,106 @@ def _metrics_eval_dev(preds, lab, ip, il, N, pix, medical):
     call("aaclip_metrics_eval", _ptr(preds), _ptr(lab), _ptr(ip), _ptr(il), N, pix, int(medical),
          ws.data_ptr() + off, need.value, _ptr(out), _stream())
     return out
+
+
+# ------------------------------------------------------------------------ few-shot memory bank
+BANK_TM = 256          # AACLIP_BANK_TILE_M: query rows per block
+BANK_TN = 256          # AACLIP_BANK_TILE_N: bank rows per tile
+BANK_MAX_SPLITS = 64   # AACLIP_BANK_MAX_SPLITS
+FUSE_HEAD = 256        # AACLIP_FEWSHOT_FUSE_HEAD
+
+
+def bank_nn_plan(M: int, Nb: int):
+    """(n_splits, tiles_per_split) of a bank_nn launch (aaclip_bank_nn_workspace; host only): split s
+    owns the bank rows [s * tiles_per_split * BANK_TN, (s + 1) * tiles_per_split * BANK_TN)."""
+    if int(M) < 1 or int(Nb) < 1:
+        raise ValueError(f"bank_nn needs at least one query row and one bank row, got {M} and {Nb}")
+    nbytes, n_splits = ctypes.c_size_t(0), ctypes.c_int(0)
+    call("aaclip_bank_nn_workspace", int(M), int(Nb), ctypes.byref(nbytes), ctypes.byref(n_splits))
+    tiles = -(-int(Nb) // BANK_TN)
+    return n_splits.value, -(-tiles // n_splits.value)
+
+
+def _bank_rows(t, name):
+    _rowmajor(t, name)
+    if t.shape[0] < 1:
+        raise ValueError(f"bank_nn: {name} has no rows")
+    if t.stride(0) < t.shape[1] or (t.stride(0) * t.element_size()) % 16 or t.data_ptr() % 16:
+        raise ValueError(f"bank_nn: {name}'s rows must be 16-byte aligned, with a row stride of at least K")
+
+
+def bank_nn(q, bank, part=None):
+    """part[m, s] = max over the bank rows of split s of q[m] . bank[n] (aaclip_bank_nn): the
+    nearest-patch search of the few-shot path, an MFMA GEMM that keeps only a running row maximum.
+    q [M, K], bank [Nb, K]: float16, bfloat16 or float32, the same for both; unit column stride, any
+    16-byte aligned row stride; K a multiple of 64; finite values. part: fp32 [M, n_splits] contiguous
+    (bank_nn_plan) or None for a fresh one; returned. max over s is the row's result (bank_distance)."""
+    _bank_rows(q, "q")
+    _bank_rows(bank, "bank")
+    if q.dtype != bank.dtype:
+        raise TypeError(f"bank_nn operands must share a dtype, got {q.dtype} and {bank.dtype}")
+    tag = dtag(q)
+    M, K = q.shape
+    Nb = bank.shape[0]
+    if bank.shape[1] != K or K % 64 or K == 0:
+        raise ValueError(f"bank_nn needs q [M, K] and bank [Nb, K] with K a multiple of 64, got {tuple(q.shape)} "
+                         f"and {tuple(bank.shape)}")
+    n_splits, _ = bank_nn_plan(M, Nb)
+    if part is None:
+        part = torch.empty(M, n_splits, device=q.device, dtype=torch.float32)
+    if part.dtype != torch.float32 or tuple(part.shape) != (M, n_splits) or not part.is_contiguous():
+        raise ValueError(f"bank_nn: part must be a contiguous float32 {(M, n_splits)} workspace, got {part.dtype} "
+                         f"{tuple(part.shape)}")
+    _dev(q, bank, part)  # after the shape / dtype checks: those need no device
+    _launch("fewshot", "bank_nn", 2.0 * M * Nb * K, (M * K + Nb * K) * q.element_size() + 4.0 * part.numel(),
+            "aaclip_bank_nn", tag, M, Nb, K, _ptr(q), q.stride(0), _ptr(bank), bank.stride(0), _ptr(part),
+            part.numel() * 4, _stream())
+    return part
+
+
+def bank_distance(part, grid, *, accumulate: bool):
+    """grid[m] = (accumulate ? grid[m] : 0) + (1 - max_s part[m, s]) (aaclip_bank_distance). part fp32
+    [M, n_splits] contiguous (bank_nn); grid contiguous fp32 of M elements, e.g. the [B, 1, g, g] grid
+    blur_upsample takes (row m = b * g * g + p). Called per level, accumulate from the second on."""
+    if part.dim() != 2 or part.dtype != torch.float32 or not part.is_contiguous() or part.numel() == 0:
+        raise ValueError("bank_distance: part must be a non-empty contiguous float32 [M, n_splits]")
+    M, n_splits = part.shape
+    if n_splits > BANK_MAX_SPLITS:
+        raise ValueError(f"bank_distance: at most {BANK_MAX_SPLITS} splits, got {n_splits}")
+    if grid.dtype != torch.float32 or not grid.is_contiguous() or grid.numel() != M:
+        raise ValueError(f"bank_distance: grid must be contiguous float32 of {M} elements, got {grid.dtype} "
+                         f"{tuple(grid.shape)}")
+    _dev(part, grid)
+    _launch("fewshot", "bank_distance", 0.0, 4.0 * part.numel() + 8.0 * M, "aaclip_bank_distance", _ptr(part), M,
+            n_splits, int(bool(accumulate)), _ptr(grid), _stream())
+    return grid
+
+
+def fewshot_fuse(zs_map, fs_map, zs_score):
+    """One class's zero-shot and few-shot results fused (aaclip_fewshot_fuse): zs_map / fs_map fp32
+    [n, ...] of equal shapes, zs_score [n]. Returns (fused_map of zs_map's shape, fs_score [n],
+    fused_score [n]): fs_score the per-image maximum of fs_map; fused = N(zero-shot) + N(few-shot),
+    N the min-max normalisation over the class (0 for a constant input). Enqueued without a host
+    sync; numpy float32 gives the same bits (tests/fewshot_ref.py)."""
+    if zs_map.dim() < 2 or zs_map.numel() == 0 or tuple(fs_map.shape) != tuple(zs_map.shape):
+        raise ValueError(f"fewshot_fuse: zs_map and fs_map must be non-empty [n, ...] of one shape, got "
+                         f"{tuple(zs_map.shape)} and {tuple(fs_map.shape)}")
+    n = zs_map.shape[0]
+    if zs_score.numel() != n:
+        raise ValueError(f"fewshot_fuse: zs_score must have one entry per image ({n}), got {tuple(zs_score.shape)}")
+    for t, name in ((zs_map, "zs_map"), (fs_map, "fs_map"), (zs_score, "zs_score")):
+        if t.dtype != torch.float32:
+            raise TypeError(f"fewshot_fuse: {name} must be float32, got {t.dtype}")
+    zs_map, fs_map, zs_score = zs_map.contiguous(), fs_map.contiguous(), zs_score.reshape(-1).contiguous()
+    with torch.cuda.device(zs_map.device):
+        _dev(zs_map, fs_map, zs_score)
+        need = ctypes.c_size_t(0)
+        call("aaclip_overlay_workspace", n, ctypes.byref(need))
+        nbytes = FUSE_HEAD + int(need.value)
+        ws, at = _aligned_workspace(nbytes, zs_map.device)
+        fused_map = torch.empty_like(zs_map)
+        fs_score = torch.empty(n, device=zs_map.device, dtype=torch.float32)
+        fused_score = torch.empty(n, device=zs_map.device, dtype=torch.float32)
+        call("aaclip_fewshot_fuse", _ptr(zs_map), _ptr(fs_map), _ptr(zs_score), n, zs_map.numel() // n, at, nbytes,
+             _ptr(fused_map), _ptr(fs_score), _ptr(fused_score), _stream())
+    return fused_map, fs_score, fused_score

@@ -218,6 +218,44 @@ class SyntheticSingleClassDataset(Dataset):
         return np.clip(np.rint((img * STD + MEAN) * 255.0), 0, 255).astype(np.uint8).transpose(1, 2, 0).copy()
 
 
+class SyntheticSupportDataset(SyntheticSingleClassDataset):
+    """The `shot` normal support images of a synthetic class (few-shot memory bank): the even
+    (label 0) items of a SyntheticSingleClassDataset whose seed lies SEED_OFFSET above the test
+    set's, so no support item is a test item (the test seeds of the synthetic datasets span 15)."""
+    SEED_OFFSET = 1000
+
+    def __init__(self, shot: int, img_size: int, class_name: str = "bottle", seed: int = 111):
+        super().__init__(shot, img_size, class_name, seed + self.SEED_OFFSET)
+
+    def __getitem__(self, idx):
+        if not 0 <= idx < self.n:
+            raise IndexError(idx)
+        item = super().__getitem__(2 * idx)
+        item["file_name"] = f"synthetic/support/{idx:05d}.png"
+        return item
+
+    def source_u8(self, idx):
+        raise NotImplementedError("support items are not visualised")
+
+
+class SupportDataset(BaseSingleClassDataset):
+    """The first `shot` normal (label 0) lines of a class in a jsonl of the reference's line format:
+    the support images of the few-shot memory bank."""
+
+    def __init__(self, data_path: str, meta_path: str, img_size: int, class_name: str, shot: int,
+                 raw: bool = False):
+        super().__init__(data_path, meta_path, img_size, class_name, raw=raw)
+        self.meta = [m for m in self.meta if m["label"] == 0][:shot]
+        if len(self.meta) < shot:
+            raise ValueError(f"{meta_path} lists {len(self.meta)} normal images of class {class_name}, "
+                             f"--shot {shot} needs {shot}")
+
+
+SUPPORT_META_MISSING = ("few-shot scoring of a real dataset needs --support_meta PATH: a jsonl in the metadata "
+                        "line format listing normal (label 0) support images per class; the reference's lists "
+                        "hold test images only, so there is no default")
+
+
 def collate_raw(items):
     """Batch raw items: uint8 images/masks stacked when the sizes agree (one
     preprocessing launch), else kept as lists (one launch per size)."""
@@ -241,15 +279,25 @@ def metadata_root() -> str:
 
 
 def get_dataset(dataset_name: str, img_size: int, training_mode: str, shot: int = -1, stage: str = "train",
-                logger=None, synthetic_n: int = 16, raw: bool = False):
+                logger=None, synthetic_n: int = 16, raw: bool = False, support_meta: str | None = None):
+    """stage "support" (few-shot memory bank): per class the `shot` normal support images -- for the
+    synthetic datasets seeded items that are no test items (SyntheticSupportDataset), for a real
+    dataset the first `shot` label-0 lines of the class in the jsonl `support_meta`."""
+    if stage == "support" and shot < 1:
+        raise ValueError(f"stage support needs a positive shot, got {shot}")
     if dataset_name in ("synthetic", "synthetic_mvtec"):
+        if stage == "support":
+            if dataset_name == "synthetic":
+                return {"bottle": SyntheticSupportDataset(shot, img_size)}
+            return {c: SyntheticSupportDataset(shot, img_size, class_name=c, seed=111 + i)
+                    for i, c in enumerate(CLASS_NAMES["synthetic_mvtec"])}
         if stage == "train":
             if dataset_name != "synthetic":
                 raise ValueError("of the synthetic datasets only 'synthetic' has a train stage")
             return (SyntheticTrainDataset(synthetic_n, img_size, text=True, raw=raw),
                     SyntheticTrainDataset(synthetic_n, img_size, text=False, raw=raw))
         if stage not in ("test", "visualize"):
-            raise ValueError(f"stage {stage} not found; available stages: train, test")
+            raise ValueError(f"stage {stage} not found; available stages: train, test, support")
         if dataset_name == "synthetic":
             return {"bottle": SyntheticSingleClassDataset(synthetic_n, img_size)}
         # config C4's shape: every MVTec class, its own seed
@@ -267,9 +315,14 @@ def get_dataset(dataset_name: str, img_size: int, training_mode: str, shot: int 
         data_path = DATA_PATH[dataset_name.split("-")[0]]
         return (BaseDataset(data_path, meta_path, img_size, text=True, raw=raw),
                 BaseDataset(data_path, meta_path, img_size, text=False, raw=raw))
+    if stage == "support":
+        if not support_meta:
+            raise ValueError(SUPPORT_META_MISSING)
+        return {c: SupportDataset(DATA_PATH[dataset_name], support_meta, img_size, c, shot, raw=raw)
+                for c in CLASS_NAMES[dataset_name]}
     if stage in ("test", "visualize"):
         meta_path = os.path.join(metadata_root(), dataset_name, "full-shot.jsonl")
         return {c: BaseSingleClassDataset(DATA_PATH[dataset_name], meta_path, img_size, c,
                                           logger=logger if stage == "test" else None, raw=raw)
                 for c in CLASS_NAMES[dataset_name]}
-    raise ValueError(f"stage {stage} not found; available stages: train, test")
+    raise ValueError(f"stage {stage} not found; available stages: train, test, support")

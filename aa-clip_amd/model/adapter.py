@@ -157,6 +157,18 @@ class AdaptedCLIP(nn.Module):
         The outputs are engine-owned buffers: clone them to keep them (test.py does)."""
         return self.visual_engine().predict_cached(x, text_features, domain, streams=streams)
 
+    def build_memory_bank(self, images):
+        """The few-shot memory bank of a class from its normal support images [k, 3, S, S]
+        (reference test.py:39-50, get_support_features): VisualEngine.build_bank."""
+        return self.visual_engine().build_bank(images)
+
+    def predict_few_shot(self, x, text_features, bank, domain="Industrial"):
+        """(zero-shot map [B,S,S], zero-shot score [B], few-shot map [B,S,S]), fp32, fresh tensors:
+        predict()'s map and score, and each patch's distance to its nearest bank patch summed over the
+        levels, blurred and upsampled (VisualEngine.predict_few_shot). A bank built at another
+        image size or search dtype raises ValueError."""
+        return self.visual_engine().predict_few_shot(x, text_features, bank, domain)
+
     def encode_text(self, text, adapt_text=True):
         if not adapt_text:
             return self.clipmodel.encode_text(text)

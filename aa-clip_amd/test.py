@@ -22,7 +22,12 @@ Differences from the reference, all on the host side:
   * --visualize hands visualize() the device tensors: the overlays are rendered on the
     device, from thumbnails made at batch time out of the photos already there (single
     process, --gpu_preprocess), from the files otherwise (rank 0 in a sharded run), and
-    for the synthetic datasets from the items un-normalised (source_u8).
+    for the synthetic datasets from the items un-normalised (source_u8);
+  * --few_shot reads --shot, which the reference parses and never uses (its test.py:39-50
+    get_support_features and utils.py:86-93 cos_sim are wired to nothing): per class a memory
+    bank of --shot normal support images (get_dataset stage "support"; real datasets list them
+    in --support_meta), every test patch scored by its distance to the nearest bank patch at
+    every level on the device, and that map fused with the zero-shot one (single process).
 """
 from __future__ import annotations
 
@@ -148,13 +153,62 @@ def get_predictions(model, class_text_embeddings, test_loader, device, img_size,
     return masks, labels, preds, preds_image, file_names
 
 
+def get_few_shot_predictions(model, class_text_embeddings, test_loader, support_loader, device, img_size,
+                             dataset="MVTec", prep=None, sources=None):
+    """get_predictions for --few_shot (single process): the class's memory bank is built from the
+    support loader's normal images (reference test.py:39-50), every test batch goes through
+    AdaptedCLIP.predict_few_shot, and the class's zero-shot and few-shot maps and scores are fused
+    on the device (aaclip_fewshot_fuse). Returns get_predictions' tuple with the fused maps and
+    scores in the place of the zero-shot ones, and a dict of the device tensors behind them:
+    zs_map, fs_map, fused_map [N,S,S], zs_score, fs_score, fused_score [N]. The bank is dropped
+    on return. Eager and on one stream; sources as in get_predictions."""
+    from aaclip import ops
+    device = torch.device(device)
+    support = [_device_batch(batch, prep, device)[0] for batch in support_loader]
+    if not support:
+        raise ValueError("few-shot scoring needs at least one support image per class")
+    bank = model.build_memory_bank(torch.cat(support))
+    del support
+    masks, labels, zs_maps, zs_scores, fs_maps, file_names = [], [], [], [], [], []
+    for input_data in test_loader:
+        thumbs = [] if (sources is not None and prep is not None) else None
+        image, mask = _device_batch(input_data, prep, device, thumbs)
+        if thumbs:
+            sources.append(thumbs[0])
+        assert len(set(input_data["class_name"])) == 1, "mixed class not supported"
+        labels.append(np.asarray(input_data["label"]))
+        file_names.extend(input_data["file_name"])
+        zs_map, zs_score, fs_map = model.predict_few_shot(image, class_text_embeddings, bank, DOMAINS[dataset])
+        zs_maps.append(zs_map)
+        zs_scores.append(zs_score)
+        fs_maps.append(fs_map)
+        masks.append(mask)
+    del bank
+    if not zs_maps:
+        raise ValueError("few-shot scoring needs at least one test image per class")
+    masks, labels = torch.cat(masks), np.concatenate(labels, axis=0)
+    zs_map, zs_score, fs_map = torch.cat(zs_maps), torch.cat(zs_scores), torch.cat(fs_maps)
+    fused_map, fs_score, fused_score = ops.fewshot_fuse(zs_map, fs_map, zs_score)
+    parts = {"zs_map": zs_map, "fs_map": fs_map, "fused_map": fused_map, "zs_score": zs_score,
+             "fs_score": fs_score, "fused_score": fused_score}
+    return masks, labels, fused_map, fused_score, file_names, parts
+
+
 def parse_args(argv=None):
     parser = argparse.ArgumentParser(description="Testing")
     parser.add_argument("--model_name", type=str, default="ViT-L-14-336", help="ViT-L-14-336")
     parser.add_argument("--img_size", type=int, default=518)
     parser.add_argument("--relu", action="store_true")
     parser.add_argument("--dataset", type=str, default="MVTec")
-    parser.add_argument("--shot", type=int, default=4)
+    parser.add_argument("--shot", type=int, default=4,
+                        help="--few_shot: normal support images per class in the memory bank (ignored otherwise)")
+    parser.add_argument("--few_shot", action="store_true",
+                        help="few-shot scoring: per class a memory bank of --shot normal support images; every "
+                             "test patch's distance to its nearest bank patch, over the levels, is fused with the "
+                             "zero-shot map and score (single process)")
+    parser.add_argument("--support_meta", type=str, default="",
+                        help="--few_shot on a real dataset: jsonl in the metadata line format listing the normal "
+                             "support images (the first --shot label-0 lines of each class are used)")
     parser.add_argument("--batch_size", type=int, default=32)
     parser.add_argument("--seed", type=int, default=111)
     parser.add_argument("--save_path", type=str, default="ckpt/baseline")
@@ -208,10 +262,15 @@ def run(args):
     anchors and every class's (masks, labels, preds, preds_image), with --f1 also
     "operating_points": per class the pixel and image F1-max threshold, precision and
     recall, with --regions also "regions": per class {"threshold", "images": [{"file_name",
-    "n_regions", "regions"}]}, see forward_utils.anomaly_regions) for callers/tests."""
+    "n_regions", "regions"}]}, see forward_utils.anomaly_regions, with --few_shot also
+    "few_shot": per class the device tensors zs_map, fs_map, fused_map, zs_score, fs_score,
+    fused_score; the class's preds and preds_image are then the fused ones) for callers/tests."""
     setup_seed(args.seed)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
+    if args.few_shot and world > 1:
+        raise RuntimeError("--few_shot runs in a single process: sharded (torchrun, WORLD_SIZE > 1) few-shot "
+                           "scoring is not supported")
     if not torch.cuda.is_available():
         raise RuntimeError("the AA-CLIP MI355X build needs a GPU (no CPU path)")
     if world > 1:  # one process per GPU (torchrun); image-sharded classes
@@ -275,6 +334,10 @@ def run(args):
         raw = args.gpu_preprocess and not synthetic  # synthetic items are already normalised
         image_datasets = get_dataset(args.dataset, args.img_size, None, args.shot, "test", logger=logger,
                                      synthetic_n=args.synthetic_n, raw=raw)
+        support_datasets = None
+        if args.few_shot:  # before any model work: a real dataset without --support_meta fails here
+            support_datasets = get_dataset(args.dataset, args.img_size, None, args.shot, "support", raw=raw,
+                                           support_meta=args.support_meta or None)
         prep = None
         if raw:
             from aaclip.preprocess import Preprocessor
@@ -290,6 +353,8 @@ def run(args):
             ctx["operating_points"] = {}
         if args.regions:
             ctx["regions"], names = {}, {}
+        if args.few_shot:
+            ctx["few_shot"] = {}
         for class_name, image_dataset in image_datasets.items():
             workers = 0 if synthetic else 4
             from dataset import collate_raw
@@ -304,10 +369,20 @@ def run(args):
                                                  collate_fn=collate_raw if raw else None)
             sources = [] if args.visualize else None
             with torch.no_grad():
-                masks, labels, preds, preds_image, file_names = get_predictions(
-                    model=model, class_text_embeddings=text_embeddings[class_name], test_loader=loader,
-                    device=device, img_size=args.img_size, dataset=args.dataset, prep=prep, n_total=n_total,
-                    streams=args.streams, sources=sources)
+                if args.few_shot:  # the class's bank lives inside this call
+                    support_loader = torch.utils.data.DataLoader(
+                        support_datasets[class_name], batch_size=args.batch_size, shuffle=False,
+                        num_workers=workers, pin_memory=True, collate_fn=collate_raw if raw else None)
+                    masks, labels, preds, preds_image, file_names, parts = get_few_shot_predictions(
+                        model=model, class_text_embeddings=text_embeddings[class_name], test_loader=loader,
+                        support_loader=support_loader, device=device, img_size=args.img_size,
+                        dataset=args.dataset, prep=prep, sources=sources)
+                    ctx["few_shot"][class_name] = parts
+                else:
+                    masks, labels, preds, preds_image, file_names = get_predictions(
+                        model=model, class_text_embeddings=text_embeddings[class_name], test_loader=loader,
+                        device=device, img_size=args.img_size, dataset=args.dataset, prep=prep, n_total=n_total,
+                        streams=args.streams, sources=sources)
             if rank != 0:  # the class was gathered onto rank 0, which runs metrics_eval
                 continue
             if args.visualize:

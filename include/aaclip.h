@@ -873,6 +873,64 @@ int aaclip_overlay_panels(const float* maps, const uint8_t* labels, const uint8_
                           int batch, int size, int swap_rb, uint8_t* out, void* stream);
 
 /*
+ * Few-shot memory-bank scoring (csrc/bank.hip). Replaces what the reference carries for it and
+ * wires to nothing: test.py:39-50 get_support_features (the bank: the level features of a few
+ * normal support images, concatenated per level) and utils.py:86-93 cos_sim (the patch x bank
+ * similarity matrix). A test patch's few-shot score at a level is 1 - its largest cosine with any
+ * bank patch; the matrix itself is never written.
+ *
+ * aaclip_bank_nn: part[m][s] = max over the bank rows n of split s of Q[m,:] . R[n,:] in fp32.
+ * Q [M, K] with row stride ldq, R [Nb, K] with row stride ldr (strides in elements), both of
+ * `dtype`: AACLIP_F16 (v_mfma_f32_16x16x32_f16), AACLIP_BF16 (the same kernel on the bf16 MFMA) or
+ * AACLIP_F32 (v_mfma_f32_16x16x4_f32). M >= 1 and Nb >= 1 are arbitrary, K % 64 == 0; Q and R 16-byte
+ * aligned with 16-byte aligned row strides >= K. The bank's tiles of AACLIP_BANK_TILE_N rows are dealt
+ * to n_splits splits, split s owning tiles [s * tps, (s + 1) * tps), tps = ceil(tiles / n_splits); a
+ * block takes one tile of AACLIP_BANK_TILE_M query rows and one split. part: caller-owned device
+ * fp32 [M][n_splits]; aaclip_bank_nn_workspace (host only, a function of M and Nb alone) gives its
+ * bytes and n_splits: of the even splits into at most AACLIP_BANK_MAX_SPLITS parts, none empty, the
+ * one whose row tiles x splits blocks take the fewest rounds x tiles at
+ * AACLIP_BANK_RESIDENT_BLOCKS blocks on the chip at once (csrc/bank.hip, bank_plan). Ragged tiles read the last row again
+ * instead of padding (a duplicate cannot move a maximum; a zero row could). Inputs must be finite.
+ * Every dot product sums K in one order wherever its row and column sit in a tile or split, so a
+ * query row's result has the same bits alone or in a batch, under any permutation of the bank rows
+ * and on every launch. No atomics.
+ *
+ * aaclip_bank_distance: grid[m] = (accumulate ? grid[m] : 0) + (1 - max_s part[m][s]), the splits
+ * read in order, fp32. Row m = b * P + p is element [b][0][p] of the [B, 1, g, g] grid that
+ * aaclip_blur_upsample takes; called once per level, accumulate != 0 from the second on (the level
+ * sum is taken ahead of the blur, as in the zero-shot path). No clamp: a self-match may give a
+ * distance a hair below 0.
+ *
+ * aaclip_fewshot_fuse: one class's zero-shot and few-shot results into the pair the metrics take.
+ * zs_map, fs_map fp32 [n_images, pix_per_image], zs_score fp32 [n_images]. With
+ * N(x; lo, hi) = (x - lo) / (hi - lo), and 0 where hi == lo (a constant input contributes 0, not NaN):
+ *   fs_score[b]    = max over the pixels of fs_map[b]
+ *   fused_map[i]   = N(zs_map[i]; zs_map's range) + N(fs_map[i]; fs_map's range)
+ *   fused_score[b] = N(zs_score[b]; zs_score's range) + N(fs_score[b]; fs_score's range)
+ * each range the class's (lo, hi) from aaclip_overlay_range (for the scores with pix_per_image = 1),
+ * every operation one rounded fp32 operation: numpy float32 gives the same bits
+ * (tests/fewshot_ref.py). workspace: 16-byte aligned caller-owned device memory of
+ * AACLIP_FEWSHOT_FUSE_HEAD + aaclip_overlay_workspace(n_images) bytes. Outputs must not overlap
+ * inputs. Inputs must be finite. Needs n_images <= 2^24.
+ *
+ * All of them return AACLIP_ERR_ARG, before any launch, for NULL pointers, non-positive sizes, a
+ * dtype outside the three, K % 64 != 0, a stride below K or not 16-byte aligned, misaligned
+ * operands or a short workspace; they allocate nothing and do not sync.
+ */
+#define AACLIP_BANK_TILE_M 256
+#define AACLIP_BANK_TILE_N 256
+#define AACLIP_BANK_RESIDENT_BLOCKS 256
+#define AACLIP_BANK_MAX_SPLITS 64
+#define AACLIP_FEWSHOT_FUSE_HEAD 256
+int aaclip_bank_nn_workspace(int M, int Nb, size_t* bytes, int* n_splits);
+int aaclip_bank_nn(int dtype, int M, int Nb, int K, const void* Q, int64_t ldq, const void* R, int64_t ldr,
+                   float* part, size_t part_bytes, void* stream);
+int aaclip_bank_distance(const float* part, int M, int n_splits, int accumulate, float* grid, void* stream);
+int aaclip_fewshot_fuse(const float* zs_map, const float* fs_map, const float* zs_score, int n_images,
+                        int64_t pix_per_image, void* workspace, size_t workspace_bytes, float* fused_map,
+                        float* fs_score, float* fused_score, void* stream);
+
+/*
  * Test-time preprocessing (replaces dataset/__init__.py:127-143
  * transform_x / transform_mask, i.e. Pillow's Image.resize as torchvision calls it,
  * then ToTensor + Normalize). Bit-exact with Pillow 8-bit resampling.
