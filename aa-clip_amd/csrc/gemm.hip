@@ -4,25 +4,34 @@
 // which is the natural MFMA "NT" form: every A and B fragment of
 // v_mfma_f32_16x16x32_bf16 is 8 consecutive K values = one 16-byte ds_read_b128.
 //
-// bf16 kernel (perf path):
-//   * block tile BM x BN x 64, 8 waves (512 threads), wave tile (BM/WM) x (BN/WN);
-//     default 320x256 (wave tile 160x64 = 10x4 MFMA tiles, 144 KiB LDS double buffer)
-//   * global -> LDS by LDS-DMA (global_load_lds_dwordx4, 1 KiB per wave
-//     instruction = 8 rows of 128 B). The LDS image is lane-linear, so the bank
-//     swizzle (16-B chunk c of row r stored at chunk c ^ (r & 7)) is applied on
-//     the per-lane SOURCE address and undone on the ds_read (rule: swizzle both
-//     sides through the same involution) -> conflict-free fragment reads.
-//   * 2-stage double buffer, one barrier per K-step: the DMA of tile k+1 is
-//     issued before the MFMAs of tile k.
+// Two kernel templates carry the 16-bit (bf16 / fp16) and fp8 operands; choose16 picks one
+// per shape (a pin or the A/B variant overrides it), and every choice accumulates K in the
+// same order, so it changes speed and never bits.
+//   * gemm_8ph_kernel<Q, H16, SCORES>: 256x256 tile, the K-step cut into 4 phases with the
+//     two wave rows in ping-pong (8-phase). The default wherever its 256-row tiles need no
+//     more rounds over the CUs than 320-row tiles would, and for every MX fp8 GEMM.
+//   * gemm_bf16_kernel<BM, BN, WM, WN, Q, H16>: block tile BM x BN, one 128-byte K-step per
+//     barrier, 2-stage double buffer (the DMA of tile k+1 is issued before the MFMAs of
+//     tile k). 320x256 where that tiling saves a round, 128x128 / 64x64 for a few images,
+//     256x128 for N % 256 != 0, 256x256 for per-row fp8 and as the MX A/B partner.
+// Shared by both:
+//   * global -> LDS by LDS-DMA (1 KiB per wave instruction = 8 rows of 128 B). The LDS
+//     image is lane-linear, so the bank swizzle (16-B chunk c of row r stored at chunk
+//     c ^ (r & 7)) is applied on the per-lane SOURCE address and undone on the ds_read
+//     (rule: swizzle both sides through the same involution) -> conflict-free fragment reads.
 //   * XCD-aware, bijective block remap + grouped tile order for L2 reuse.
-//   * fused epilogue: bias, erf-GELU, LeakyReLU, fp32 residual, bf16 aux copy,
-//     output row remap (patch rows -> token rows after the CLS slot).
+//   * fused epilogue: bias, erf-GELU / QuickGELU, LeakyReLU, fp32 residual, 16-bit aux copy,
+//     output row remap (patch rows -> token rows after the CLS slot), MX fp8 output, score
+//     partials. wave_epilogue stores straight from the accumulators, wave_epilogue_lds
+//     (8-phase) quad-coalesced through LDS; the bias / scale loads, the activation chain,
+//     the MX quantisation and the c_mx address are one copy both call (epi_*, mx_quant_row).
 // fp32 kernel (parity mode): v_mfma_f32_16x16x4_f32 (exact fp32 FMA chain),
-//   64x64x16 register-staged tiles. Same epilogue.
+//   64x64x16 register-staged tiles. Same epilogue, one element at a time.
 #include <math.h>
 
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 
 #include "common.h"
 
@@ -169,6 +178,70 @@ __device__ __forceinline__ uint4 pair_h16(const float4_t& lo, const float4_t& hi
   return uint4{x[0], y[0], x[1], y[1]};
 }
 
+// ---- the epilogue pieces both wave epilogues share. One copy, one operation order: that is
+// what keeps "a pin changes speed, never bits" true across the two store layouts. (The
+// acc * scale + bias line and the residual ring stay written out in each epilogue: moved into a
+// helper, either one changes the register allocation of the run-time-flag instantiations.)
+__device__ __forceinline__ int epi_out_row(const GemmArgs& a, int epi, int m) {
+  return (epi & EPI_REMAP) ? remap_row(a, m) : m;
+}
+
+// bias (lbias: the tile's bias staged in LDS by the kernel, indexed by column) and, for fp8, the
+// per-column weight scales of this lane's 4 columns ncol + 16 j .. + 3 in every column tile j
+template <int RN, int SCALED>
+__device__ __forceinline__ void epi_load_cols(const GemmArgs& a, int epi, const float* lbias, int ncol,
+                                              float4_t (&bias)[RN], float4_t (&wsc)[RN]) {
+#pragma unroll
+  for (int j = 0; j < RN; ++j)
+    bias[j] = (epi & AACLIP_EPI_BIAS) ? *(const float4_t*)((lbias ? lbias : a.bias) + ncol + 16 * j)
+                                      : float4_t{0.f, 0.f, 0.f, 0.f};
+  if constexpr (SCALED) {
+#pragma unroll
+    for (int j = 0; j < RN; ++j) wsc[j] = *(const float4_t*)(a.w_scale + ncol + 16 * j);
+  }
+}
+
+// MX quantisation of one row's 64-column block (lane (fr, fq) holds columns 16 j + 4 fq .. + 3
+// of tile j): row max over the 4 lane groups, power-of-two scale, RNE to e4m3, 4x4 lane-group
+// transpose. On exit d = the row's bytes 16 fq .. 16 fq + 15; returns the block exponent.
+__device__ __forceinline__ int mx_quant_row(const float4_t (&v)[4], uint32_t (&d)[4]) {
+  float amax = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) amax = fmaxf(amax, fabsf(v[j][t]));
+  const int e = mx_exp(max_over_fq(amax));
+  const float inv = pow2i(-e);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    uint32_t w = __builtin_amdgcn_cvt_pk_fp8_f32(v[j][0] * inv, v[j][1] * inv, 0, false);
+    d[j] = __builtin_amdgcn_cvt_pk_fp8_f32(v[j][2] * inv, v[j][3] * inv, w, true);
+  }
+  transpose_fq(d);
+  return e;
+}
+
+// the e8m0 byte of output row orow for the 64-column block that starts at column nw
+__device__ __forceinline__ uint8_t* c_mx_addr(const GemmArgs& a, int nw, size_t orow) {
+  const int blk = nw >> 6;
+  return a.c_mx + ((size_t)(blk >> 1) * a.ld_cmx + orow) * 2 + (blk & 1);
+}
+
+// the activation under EPI, on a lane's 4 columns of one column tile
+__device__ __forceinline__ void epi_activate(int epi, float4_t& v) {
+  if (epi & AACLIP_EPI_GELU) {
+    const float2_t lo = gelu_fast2(float2_t{v[0], v[1]}), hi = gelu_fast2(float2_t{v[2], v[3]});
+    v = float4_t{lo[0], lo[1], hi[0], hi[1]};
+  }
+  if (epi & AACLIP_EPI_QGELU) {
+    const float2_t lo = qgelu_fast2(float2_t{v[0], v[1]}), hi = qgelu_fast2(float2_t{v[2], v[3]});
+    v = float4_t{lo[0], lo[1], hi[0], hi[1]};
+  }
+  if (epi & AACLIP_EPI_LEAKY)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) v[t] = v[t] >= 0.f ? v[t] : 0.01f * v[t];
+}
+
 // EPI >= 0: compile-time epilogue flags (AACLIP_EPI_* | EPI_REMAP) so each used
 // combination is straight-line code; EPI = -1: flags read at run time (any combination).
 // OUTM: 0 = fp32 C, 1 = bf16 C, 2 = fp8 e4m3 C with an e8m0 scale per (row, 64
@@ -186,14 +259,10 @@ __device__ __forceinline__ void wave_epilogue(const GemmArgs& a, float4_t (&acc)
   constexpr bool BF16OUT = OUTM == 1;
   const int fr = lane & 15, fq = lane >> 4;
   const int epi = EPI >= 0 ? EPI : a.epi | (a.row_group > 0 ? EPI_REMAP : 0);
-  auto out_row = [&](int m) { return (epi & EPI_REMAP) ? remap_row(a, m) : m; };
   const int ncol = nw + 4 * fq;               // fp32 layout: this lane's first column in tile j = 0
   const int pcol = nw + 16 * (fq & 1) + 8 * (fq >> 1);  // paired bf16 layout
-  float4_t bias[RN];
-#pragma unroll
-  for (int j = 0; j < RN; ++j)  // lbias: the tile's bias staged in LDS by the kernel (indexed by column)
-    bias[j] = (epi & AACLIP_EPI_BIAS) ? *(const float4_t*)((lbias ? lbias : a.bias) + ncol + 16 * j)
-                                      : float4_t{0.f, 0.f, 0.f, 0.f};
+  float4_t bias[RN], wsc[RN];
+  epi_load_cols<RN, SCALED>(a, epi, lbias, ncol, bias, wsc);
   // OUTM 3 (score partials): this lane's anchor values, t0 / t1 of columns ncol + 16 j + e
   float4_t ta0[RN], ta1[RN];
   if constexpr (OUTM == 3) {
@@ -205,11 +274,6 @@ __device__ __forceinline__ void wave_epilogue(const GemmArgs& a, float4_t (&acc)
       ta1[j] = float4_t{lo[1], lo[3], hi[1], hi[3]};
     }
   }
-  float4_t wsc[RN];  // fp8: per-column weight scales of this lane's 4 columns in tile j
-  if constexpr (SCALED) {
-#pragma unroll
-    for (int j = 0; j < RN; ++j) wsc[j] = *(const float4_t*)(a.w_scale + ncol + 16 * j);
-  }
   // residual rows in a PD-deep register ring: tile-row i + PD - 1 is requested before
   // tile-row i is used. PD = 4 on the 8-phase kernel (244 VGPRs, no spill) measured
   // 0.4 % SLOWER in the two-stream step than PD = 2 (224 VGPRs): above 224 the 8-wave
@@ -217,7 +281,7 @@ __device__ __forceinline__ void wave_epilogue(const GemmArgs& a, float4_t (&acc)
   static_assert(PD >= 2 && PD <= RM, "residual ring depth");
   float4_t res[PD][RN];
   auto load_res = [&](int i, float4_t (&dst)[RN]) {
-    const float* src = a.res + (size_t)out_row(min(mw + 16 * i + fr, a.M - 1)) * a.ldr + ncol;
+    const float* src = a.res + (size_t)epi_out_row(a, epi, min(mw + 16 * i + fr, a.M - 1)) * a.ldr + ncol;
 #pragma unroll
     for (int j = 0; j < RN; ++j) dst[j] = *(const float4_t*)(src + 16 * j);
   };
@@ -239,17 +303,7 @@ __device__ __forceinline__ void wave_epilogue(const GemmArgs& a, float4_t (&acc)
         v[j] = acc[i][j] * wsc[j] + bias[j];
       else
         v[j] = acc[i][j] + bias[j];
-      if (epi & AACLIP_EPI_GELU) {
-        const float2_t lo = gelu_fast2(float2_t{v[j][0], v[j][1]}), hi = gelu_fast2(float2_t{v[j][2], v[j][3]});
-        v[j] = float4_t{lo[0], lo[1], hi[0], hi[1]};
-      }
-      if (epi & AACLIP_EPI_QGELU) {
-        const float2_t lo = qgelu_fast2(float2_t{v[j][0], v[j][1]}), hi = qgelu_fast2(float2_t{v[j][2], v[j][3]});
-        v[j] = float4_t{lo[0], lo[1], hi[0], hi[1]};
-      }
-      if (epi & AACLIP_EPI_LEAKY)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) v[j][t] = v[j][t] >= 0.f ? v[j][t] : 0.01f * v[j][t];
+      epi_activate(epi, v[j]);
       if (epi & AACLIP_EPI_RESID) v[j] += res[i % PD][j];
     }
     if (a.dbg & 2) {  // diagnostic: everything but the global stores
@@ -258,7 +312,7 @@ __device__ __forceinline__ void wave_epilogue(const GemmArgs& a, float4_t (&acc)
       continue;
     }
     const int m = mw + 16 * i + fr;
-    const size_t orow = (size_t)out_row(min(m, a.M - 1));
+    const size_t orow = (size_t)epi_out_row(a, epi, min(m, a.M - 1));
     if constexpr (OUTM == 3) {
       // anomaly-map partials of row m over each 32-column group (column tiles 2q, 2q+1):
       // ||v||^2, v.t0, v.t1 -- lane-local fixed-order FMA chains over its 8 values, then
@@ -285,24 +339,11 @@ __device__ __forceinline__ void wave_epilogue(const GemmArgs& a, float4_t (&acc)
       continue;
     }
     if constexpr (OUTM == 2) {
-      float amax = 0.f;
-#pragma unroll
-      for (int j = 0; j < RN; ++j)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) amax = fmaxf(amax, fabsf(v[j][t]));
-      const int e = mx_exp(max_over_fq(amax));
-      const float inv = pow2i(-e);
       uint32_t d[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        uint32_t w = __builtin_amdgcn_cvt_pk_fp8_f32(v[j][0] * inv, v[j][1] * inv, 0, false);
-        d[j] = __builtin_amdgcn_cvt_pk_fp8_f32(v[j][2] * inv, v[j][3] * inv, w, true);
-      }
-      transpose_fq(d);
+      const int e = mx_quant_row(v, d);
       if (m < a.M) {
         *(uint4*)((uint8_t*)a.C + orow * a.ldc + nw + 16 * fq) = uint4{d[0], d[1], d[2], d[3]};
-        const int blk = nw >> 6;
-        if (fq == 0) a.c_mx[((size_t)(blk >> 1) * a.ld_cmx + orow) * 2 + (blk & 1)] = (uint8_t)(e + 127);
+        if (fq == 0) *c_mx_addr(a, nw, orow) = (uint8_t)(e + 127);
       }
       continue;
     }
@@ -349,29 +390,19 @@ __device__ __forceinline__ void wave_epilogue_lds(const GemmArgs& a, float4_t (&
                                                   int lane, const float* lbias, char* slot) {
   static_assert(RN == 4 && OUTM >= 0 && OUTM <= 2, "one wave's 64 columns: fp32, 16-bit or fp8 MX rows");
   static_assert(SCALED == 0 || SCALED == 2, "no per-row A scales");
-  static_assert(PD >= 2 && PD <= RM, "residual ring depth");
   constexpr bool BF16OUT = OUTM == 1;
   const int fr = lane & 15, fq = lane >> 4;
   const int qr = lane >> 2, qc = lane & 3;  // read-back layout: row, first 16-B chunk
   const int epi = EPI >= 0 ? EPI : a.epi | (a.row_group > 0 ? EPI_REMAP : 0);
-  auto out_row = [&](int m) { return (epi & EPI_REMAP) ? remap_row(a, m) : m; };
-  const int ncol = nw + 4 * fq;
-  float4_t bias[RN];
-#pragma unroll
-  for (int j = 0; j < RN; ++j)
-    bias[j] = (epi & AACLIP_EPI_BIAS) ? *(const float4_t*)((lbias ? lbias : a.bias) + ncol + 16 * j)
-                                      : float4_t{0.f, 0.f, 0.f, 0.f};
-  float4_t wsc[RN];  // fp8: per-column weight scales of this lane's 4 columns in tile j
-  if constexpr (SCALED) {
-#pragma unroll
-    for (int j = 0; j < RN; ++j) wsc[j] = *(const float4_t*)(a.w_scale + ncol + 16 * j);
-  }
+  float4_t bias[RN], wsc[RN];
+  epi_load_cols<RN, SCALED>(a, epi, lbias, nw + 4 * fq, bias, wsc);
   const int fw = ((fr & 3) << 2) | (fr >> 2), fqr = ((qr & 3) << 2) | (qr >> 2);
   const int gw = (((fr >> 1) & 1) << 2) | ((fr >> 2) & 3), gqr = (((qr >> 1) & 1) << 2) | ((qr >> 2) & 3);
-  // residual of group i (read-back layout: row mw + 16 i + qr, columns nw + 4 qc + 16 k)
+  // residual of group i in the read-back layout: row mw + 16 i + qr, columns nw + 4 qc + 16 k
+  static_assert(PD >= 2 && PD <= RM, "residual ring depth");
   float4_t res[PD][4];
   auto load_res = [&](int i, float4_t (&dst)[4]) {
-    const float* src = a.res + (size_t)out_row(min(mw + 16 * i + qr, a.M - 1)) * a.ldr + nw + 4 * qc;
+    const float* src = a.res + (size_t)epi_out_row(a, epi, min(mw + 16 * i + qr, a.M - 1)) * a.ldr + nw + 4 * qc;
 #pragma unroll
     for (int k = 0; k < 4; ++k) dst[k] = *(const float4_t*)(src + 16 * k);
   };
@@ -391,35 +422,13 @@ __device__ __forceinline__ void wave_epilogue_lds(const GemmArgs& a, float4_t (&
         v[j] = acc[i][j] * wsc[j] + bias[j];
       else
         v[j] = acc[i][j] + bias[j];
-      if (epi & AACLIP_EPI_GELU) {
-        const float2_t lo = gelu_fast2(float2_t{v[j][0], v[j][1]}), hi = gelu_fast2(float2_t{v[j][2], v[j][3]});
-        v[j] = float4_t{lo[0], lo[1], hi[0], hi[1]};
-      }
-      if (epi & AACLIP_EPI_QGELU) {
-        const float2_t lo = qgelu_fast2(float2_t{v[j][0], v[j][1]}), hi = qgelu_fast2(float2_t{v[j][2], v[j][3]});
-        v[j] = float4_t{lo[0], lo[1], hi[0], hi[1]};
-      }
-      if (epi & AACLIP_EPI_LEAKY)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) v[j][t] = v[j][t] >= 0.f ? v[j][t] : 0.01f * v[j][t];
+      epi_activate(epi, v[j]);
     }
     const int m = mw + 16 * i + qr;
-    const size_t orow = (size_t)out_row(min(m, a.M - 1));
+    const size_t orow = (size_t)epi_out_row(a, epi, min(m, a.M - 1));
     if constexpr (OUTM == 2) {
-      float amax = 0.f;
-#pragma unroll
-      for (int j = 0; j < RN; ++j)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) amax = fmaxf(amax, fabsf(v[j][t]));
-      const int e = mx_exp(max_over_fq(amax));
-      const float inv = pow2i(-e);
       uint32_t d[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        uint32_t w = __builtin_amdgcn_cvt_pk_fp8_f32(v[j][0] * inv, v[j][1] * inv, 0, false);
-        d[j] = __builtin_amdgcn_cvt_pk_fp8_f32(v[j][2] * inv, v[j][3] * inv, w, true);
-      }
-      transpose_fq(d);  // lane (fr, fq): row fr, bytes 16 fq .. 16 fq + 15
+      const int e = mx_quant_row(v, d);  // lane (fr, fq): row fr, bytes 16 fq .. 16 fq + 15
       *(uint4*)(slot + (4 * fr + (fq ^ (fr >> 2))) * 16) = uint4{d[0], d[1], d[2], d[3]};
       const uint4 w = *(const uint4*)(slot + (4 * qr + (qc ^ (qr >> 2))) * 16);
       if (a.dbg & 2) {
@@ -428,10 +437,7 @@ __device__ __forceinline__ void wave_epilogue_lds(const GemmArgs& a, float4_t (&
       }
       if (m < a.M) *(uint4*)((uint8_t*)a.C + orow * a.ldc + nw + 16 * qc) = w;
       const int mr = mw + 16 * i + fr;  // the block scale: one byte per row, lanes fq = 0
-      if (mr < a.M && fq == 0) {
-        const int blk = nw >> 6;
-        a.c_mx[((size_t)(blk >> 1) * a.ld_cmx + out_row(mr)) * 2 + (blk & 1)] = (uint8_t)(e + 127);
-      }
+      if (mr < a.M && fq == 0) *c_mx_addr(a, nw, epi_out_row(a, epi, mr)) = (uint8_t)(e + 127);
       continue;
     }
     if (BF16OUT && !(epi & AACLIP_EPI_RESID)) {
@@ -747,20 +753,19 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs a) {
     }
 }
 
-// ================================ 8-phase ping-pong bf16 kernel (256x256x64)
+// ===================== 8-phase ping-pong kernel (256x256, one 128-byte K-step per stage)
 // The K-step is cut into 4 phases, one per C quadrant of the wave tile (64x32 =
-// 4x2 MFMA tiles x 2 k-halves = 16 MFMAs). Each phase: ds_read the quadrant's
-// register subtile, issue ONE 16-KiB LDS region of a later K-step (2 LDS-DMA per
-// thread), counted vmcnt, barrier, MFMA cluster, barrier. The two wave rows are
-// staggered by one barrier, so on every SIMD one wave runs its MFMA cluster while
-// the other issues its LDS reads and DMA (ping-pong). LDS per stage = 4 regions of
-// 128 rows x 128 B grouped by the phase that first reads them:
+// 4x2 MFMA tiles). Each phase: ds_read the quadrant's register subtile, issue ONE 16-KiB
+// LDS region of a later K-step (2 LDS-DMA per thread), counted vmcnt, barrier, MFMA
+// cluster, barrier. The two wave rows are staggered by one barrier, so on every SIMD one
+// wave runs its MFMA cluster while the other issues its LDS reads and DMA (ping-pong).
+// LDS per stage = 4 regions of 128 rows x 128 B grouped by the phase that first reads them:
 //   A0 = rows {0..63, 128..191} (A sub-block 0 of both wave rows), A1 = the other
 //   rows, B0 / B1 = the first / second 32 W-rows of every wave column.
 // Phase reads: P1 A0+B0, P2 B1, P3 A1, P4 -- and issues (K-step k): P1 B1(k+1),
 // P2 A1(k+1), P3 A0(k+2), P4 B0(k+2): every region is rewritten >= 2 phases after
-// its last read (WAR) and lands 5-6 phases before it is read; each phase's
-// vmcnt(8) (4 regions of 2 DMAs in flight) retires the region the next phase
+// its last read (WAR) and lands 5-6 phases before it is read; each phase's counted
+// vmcnt (4 regions of 2 DMAs in flight) retires the region the next phase
 // reads (RAW: read one phase after the wait, past both groups' barriers).
 // The last two K-steps issue nothing past the end and count their waits down (below).
 // Operands via buffer descriptors (rows >= M read as zero; outputs dropped by the
@@ -768,44 +773,83 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmArgs a) {
 // (A persistent form -- one workgroup per CU walking tiles, the next tile's first
 // K-steps fetched by the phantom loads under the epilogue -- measured -1.0 % in the C2
 // step and was removed in round 5; it is in the round-4 history, family 5.)
-// SCORES: the instantiation for aaclip_gemm_scores (OUTM 3 epilogue only), so the
-// anomaly-map partials path adds no registers to the block-GEMM instantiations.
-// LDS bytes of a launch: the two-stage ring, the tile's staged bias (+ the phase stamps in
-// the diagnostic build)
+// Q = 0: 16-bit operands (H16: fp16, else bf16), K-step 64, a phase is 16 MFMAs (4x2 tiles
+//   x 2 k-halves), steady-state wait vmcnt(8). The tile's bias is staged in LDS behind the
+//   ring. SCORES: the instantiation for aaclip_gemm_scores (OUTM 3 epilogue only), so the
+//   anomaly-map partials path adds no registers to the block-GEMM instantiations.
+// Q = 2: fp8 MX, e4m3 operands, K-step 128, a phase is 4x2 K=128 MFMAs (256 cycles, as 16
+//   bf16 MFMAs). The A tile's e8m0 block scales (512 B per K-step) ride in a 3-slot LDS
+//   ring behind the tile ring, issued in P3 with region A0: every wave issues one dword
+//   LDS-DMA there (waves 0-1 carry the 512 B, waves 2-7 write a scratch area nobody reads)
+//   so the per-phase DMA counts (2, 2, 3, 2) are uniform and any 4 consecutive phases hold
+//   9 -> vmcnt(9). Slot (k+2)%3 is rewritten at P3(k), 4 phases after K-step k-1's last
+//   scale read.
+// Everything that differs between the two is under `if constexpr`: no run-time branch enters
+// the K-step body (see issue_sc).
 #ifdef AACLIP_PHASE_STAMPS
-constexpr int k8phLdsBytes = 2 * 4 * 128 * 128 + 1024 + 8 * 8 * 4 * 2 * 8;
+// diagnostic build (tools/ab_build.sh ... -DAACLIP_PHASE_STAMPS, tools/gemm_phase_stamps.py): every
+// wave of the 16-bit kernel stamps s_memtime at the start and the end of each MFMA cluster of K-steps
+// 4..11 (taken right after the pre-cluster lgkmcnt(0) and after the cluster), kept in LDS and copied to
+// a.aux at the end in place of the 4 stamps of variant bit 11 (needs K >= 768).
+// The previous phase's pair is stored at the next cluster start, right after that phase's
+// lgkmcnt(0) has retired both s_memtime reads: the stamps add no wait of their own
+constexpr int kPS0 = 4, kPSN = 8;  // K-steps stamped
+#define PHASE_STAMP_A                                                                       \
+  if constexpr (!MX) {                                                                      \
+    const int q_ = ps_i - 1 - 4 * kPS0;                                                     \
+    if (q_ >= 0 && q_ < 4 * kPSN && lane == 0) {                                            \
+      ps_lds[2 * q_] = ps_a;                                                                \
+      ps_lds[2 * q_ + 1] = ps_b;                                                            \
+    }                                                                                       \
+    ps_a = __builtin_amdgcn_s_memtime();                                                    \
+  }
+#define PHASE_STAMP_B \
+  if constexpr (!MX) ps_b = __builtin_amdgcn_s_memtime();
+#define PHASE_STAMP_STORE \
+  if constexpr (!MX) ++ps_i;
 #else
-constexpr int k8phLdsBytes = 2 * 4 * 128 * 128 + 1024;
+#define PHASE_STAMP_A
+#define PHASE_STAMP_B
+#define PHASE_STAMP_STORE
 #endif
 
-template <bool H16, bool SCORES = false>
-__global__ __launch_bounds__(512) void gemm_bf16_8ph_kernel(GemmArgs a) {
-  AACLIP_TRACE_SCOPE(TR_GEMM_8PH | gemm_trace_tag(a));
-  using V8 = h16x8_t<H16>;
+template <int Q, bool H16, bool SCORES>
+__global__ __launch_bounds__(512) void gemm_8ph_kernel(GemmArgs a) {
+  static_assert(Q == 0 || (Q == 2 && !H16 && !SCORES), "16-bit operands or fp8 MX");
+  constexpr bool MX = Q == 2;
+  AACLIP_TRACE_SCOPE((MX ? TR_GEMM_FP8MX : TR_GEMM_8PH) | gemm_trace_tag(a));
+  constexpr int ES = MX ? 1 : 2;    // element bytes
+  constexpr int BK = 128 / ES;      // K elements per 128-byte step
+  constexpr int KK = MX ? 1 : 2;    // fragments per row and K-step: one of 32 bytes, or the two 16-byte k-halves
+  constexpr int WAIT = MX ? 9 : 8;  // DMAs of 4 consecutive phases: the steady-state vmcnt
+  using Frag = typename std::conditional<MX, i32x8_t, h16x8_t<H16>>::type;
   constexpr int BM = 256, BN = 256, TM = 128, TN = 64, RM = 8, RN = 4;
   constexpr int REGION = 128 * 128;                 // bytes per LDS region
   constexpr int STAGE = 4 * REGION;                 // A0, A1, B0, B1
+  constexpr int SCB = 2 * STAGE, SC_SLOT = 512;     // MX: 3 scale slots, then 6 x 256 B scratch
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int t = threadIdx.x;
   const int lane = t & 63;
   const int wid = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wr = wid >> 2, wc = wid & 3;
   const int fr = lane & 15, fq = lane >> 4;
-  const auto ars = __builtin_amdgcn_make_buffer_rsrc((void*)a.A, 0, (int)((uint32_t)a.M * (uint32_t)a.lda * 2u),
+  const auto ars = __builtin_amdgcn_make_buffer_rsrc((void*)a.A, 0, (int)((uint32_t)a.M * (uint32_t)a.lda * ES),
                                                      0x00020000);
-  const auto wrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.W, 0, (int)((uint32_t)a.N * (uint32_t)a.ldw * 2u),
+  const auto wrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.W, 0, (int)((uint32_t)a.N * (uint32_t)a.ldw * ES),
                                                      0x00020000);
+  const auto srs =
+      __builtin_amdgcn_make_buffer_rsrc((void*)a.a_mx, 0, MX ? (int)((a.K / 128) * a.ld_amx * 2) : 0, 0x00020000);
   // DMA: thread t fills row t/8 of a 64-row piece, physical 16-B chunk t%8 holds
   // logical chunk (t%8) ^ (row%8) (row%8 = (t/8)%8 in every piece)
   const int prow = t >> 3;
-  const int pchunk = ((t & 7) ^ (prow & 7)) * 8;
-  auto a_vo_of = [&](int m0) { return ((m0 + prow) * (int)a.lda + pchunk) * 2; };
-  auto w_vo_of = [&](int n0) { return ((n0 + ((prow >> 5) & 1) * 64 + (prow & 31)) * (int)a.ldw + pchunk) * 2; };
-  const int a_row = (int)a.lda * 2, w_row = (int)a.ldw * 2;  // bytes per row
-  const int nk = a.K / 64;
+  const int pchunk = ((t & 7) ^ (prow & 7)) * (16 / ES);
+  const int a_row = (int)a.lda * ES, w_row = (int)a.ldw * ES;  // bytes per row
+  const int nk = a.K / BK;
   int tm, tn;
   tile_coords(blockIdx.x, a.tiles_m, a.tiles_n, tm, tn, a.group_m);
-  const int avo = a_vo_of(tm * BM), wvo = w_vo_of(tn * BN);
+  const int m0 = tm * BM, n0 = tn * BN;
+  const int avo = ((m0 + prow) * (int)a.lda + pchunk) * ES;
+  const int wvo = ((n0 + ((prow >> 5) & 1) * 64 + (prow & 31)) * (int)a.ldw + pchunk) * ES;
   // region r of K-step kt into stage kt&1 (r: 0 = A0, 1 = A1, 2 = B0, 3 = B1)
   auto issue = [&](int r, int kt) {
     const int kc = kt * 128;
@@ -820,253 +864,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_8ph_kernel(GemmArgs a) {
                                                  (g * 128 + (r - 2) * 32) * w_row + kc, 0, 0);
     }
   };
-  // fragment offsets inside a region: local row (A: wr*64 + 16i + fr, B: wc*32 + 16j + fr),
-  // 16-B chunk (kk*4 + fq) ^ (fr & 7)
-  int a_rd[2], b_rd[2];
-#pragma unroll
-  for (int kk = 0; kk < 2; ++kk) {
-    const int sw = ((kk * 4 + fq) ^ (fr & 7)) << 4;
-    a_rd[kk] = (wr * 64 + fr) * 128 + sw;
-    b_rd[kk] = 2 * REGION + (wc * 32 + fr) * 128 + sw;
-  }
-  float4_t acc[RM][RN];
-  V8 af[4][2], bfr[2][2][2];  // A sub-block (4 tiles x kk), B sub-blocks [q][j][kk]
-
-  // the tile's 256 bias values into LDS behind the ring (one 1-KiB DMA by wave 0, retired by
-  // the prologue's vmcnt(8) as the oldest op): the epilogue reads them from LDS instead of
-  // waiting out a global-load round trip at its start
-  const bool lds_bias = !SCORES && (a.epi & AACLIP_EPI_BIAS);
-  if (lds_bias && wid == 0) {
-    const auto brs = __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, (int)((uint32_t)a.N * 4u), 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(brs, LDS_PTR(smem + 2 * STAGE), 16, (tn * BN + 4 * lane) * 4, 0, 0, 0);
-  }
-  // prologue: all of K-step 0, then A0 / B0 of K-step 1 (the steady state's P3/P4 of K-step -1)
-  issue(0, 0);
-  issue(2, 0);
-  issue(3, 0);
-  issue(1, 0);
-  if (nk > 1) {
-    issue(0, 1);
-    issue(2, 1);
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // A0(0), B0(0) landed
-  } else {
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // one K-step: B1(0), A1(0) may fly
-  }
-  __builtin_amdgcn_s_barrier();
-  if (wr == 1) __builtin_amdgcn_s_barrier();  // stagger: wave row 1 runs one barrier behind
-  // No s_setprio flips around the MFMA clusters (the sched_barrier fences already pin each
-  // cluster between its barriers): C2 step +0.8 % over setprio 1/0 around every cluster;
-  // a static prio 1 for the younger wave row measured the same as none, keeping the flips
-  // for the older row -2.5 % (profiles/r04/gemm_8ph_priority_ab.txt)
-
-  auto mfma_q = [&](int qa, int qb) {
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[qa * 4 + i][qb * 2 + j] = mfma16(bfr[qb][j][kk], af[i][kk], acc[qa * 4 + i][qb * 2 + j]);
-  };
-  auto read_a = [&](const char* st, int q) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) af[i][kk] = *(const V8*)(st + q * REGION + a_rd[kk] + i * 2048);
-  };
-  auto read_b = [&](const char* st, int q) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-        bfr[q][j][kk] = *(const V8*)(st + q * REGION + b_rd[kk] + j * 2048);
-  };
-#define PH_SYNC_MFMA(QA, QB, W)                              \
-  asm volatile("s_waitcnt vmcnt(" #W ")" ::: "memory");      \
-  __builtin_amdgcn_s_barrier();                              \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         \
-  PHASE_STAMP_A                                              \
-  __builtin_amdgcn_sched_barrier(0);                         \
-  mfma_q(QA, QB);                                            \
-  __builtin_amdgcn_sched_barrier(0);                         \
-  PHASE_STAMP_B                                              \
-  __builtin_amdgcn_s_barrier();                              \
-  PHASE_STAMP_STORE
-
-  const bool bf16_out = a.out_dtype != AACLIP_F32;
-  const int key = a.epi | (a.row_group > 0 ? EPI_REMAP : 0);
-  // diagnostic stamps (variant bit 11): shader-clock s_memtime at kernel start, main-loop
-  // end, epilogue issued, epilogue stores complete -> a.aux
-  const bool stamp = (a.dbg & 4) && a.aux && !(a.epi & AACLIP_EPI_AUX_BF16);
-#ifdef AACLIP_PHASE_STAMPS
-  // diagnostic build (tools/ab_build.sh ... -DAACLIP_PHASE_STAMPS, tools/gemm_phase_stamps.py): every
-  // wave stamps s_memtime at the start and the end of each MFMA cluster of K-steps 4..11 (taken right
-  // after the pre-cluster lgkmcnt(0) and after the cluster), kept in LDS and copied to a.aux at the end
-  // in place of the 4 stamps of variant bit 11 (needs K >= 768)
-  constexpr int kPS0 = 4, kPSN = 8;  // K-steps stamped
-  uint64_t* const ps_lds = (uint64_t*)(smem + 2 * STAGE + 1024) + wid * kPSN * 4 * 2;
-  int ps_i = 0;  // phase index since kernel start
-  uint64_t ps_a = 0, ps_b = 0;
-  // the previous phase's pair is stored at the next cluster start, right after that phase's
-  // lgkmcnt(0) has retired both s_memtime reads: the stamps add no wait of their own
-#define PHASE_STAMP_A                                                                       \
-  {                                                                                         \
-    const int q_ = ps_i - 1 - 4 * kPS0;                                                     \
-    if (q_ >= 0 && q_ < 4 * kPSN && lane == 0) {                                            \
-      ps_lds[2 * q_] = ps_a;                                                                \
-      ps_lds[2 * q_ + 1] = ps_b;                                                            \
-    }                                                                                       \
-    ps_a = __builtin_amdgcn_s_memtime();                                                    \
-  }
-#define PHASE_STAMP_B ps_b = __builtin_amdgcn_s_memtime();
-#define PHASE_STAMP_STORE ++ps_i;
-#else
-#define PHASE_STAMP_A
-#define PHASE_STAMP_B
-#define PHASE_STAMP_STORE
-#endif
-  uint64_t ts[4] = {0, 0, 0, 0};
-  if (stamp) ts[0] = __builtin_amdgcn_s_memtime();
-  const int m0 = tm * BM, n0 = tn * BN;
-#pragma unroll
-  for (int i = 0; i < RM; ++i)
-#pragma unroll
-    for (int j = 0; j < RN; ++j) acc[i][j] = float4_t{0.f, 0.f, 0.f, 0.f};
-  // One K-step: P1 A0 x B0, P2 A0 x B1, P3 A1 x B1, P4 A1 x B0, each phase's counted wait
-  // W1..W4; I1 / I2: the K-step issues its regions of K-steps kt+1 / kt+2.
-#define PH_KSTEP(KT, W1, W2, W3, W4, I1, I2)        \
-  {                                                 \
-    const char* st = smem + ((KT) & 1) * STAGE;     \
-    read_b(st, 0);                                  \
-    read_a(st, 0);                                  \
-    if (I1) issue(3, (KT) + 1);                     \
-    PH_SYNC_MFMA(0, 0, W1)                          \
-    read_b(st, 1);                                  \
-    if (I1) issue(1, (KT) + 1);                     \
-    PH_SYNC_MFMA(0, 1, W2)                          \
-    read_a(st, 1);                                  \
-    if (I2) issue(0, (KT) + 2);                     \
-    PH_SYNC_MFMA(1, 1, W3)                          \
-    if (I2) issue(2, (KT) + 2);                     \
-    PH_SYNC_MFMA(1, 0, W4)                          \
-  }
-  int kt = 0;
-  for (; kt < nk - 2; ++kt) PH_KSTEP(kt, 8, 8, 8, 8, true, true)
-  // The last two K-steps issue nothing past the last K-step: in K-step nk-2 P3 / P4 issue
-  // nothing, so P4 waits for A0 / B0 of nk-1 with only B1 / A1 of nk-1 left in flight
-  // (vmcnt 4); in K-step nk-1 P1 leaves A1 (vmcnt 2) and P2 drains. (Until round 5 the
-  // steady-state body ran to the end with phantom re-reads of the last K-step -- 1.5 K-steps
-  // of DMA per tile nobody read, still in flight ahead of the epilogue's own loads.)
-  if (nk >= 2) {
-    PH_KSTEP(kt, 8, 8, 8, 4, true, false)
-    ++kt;
-  }
-  PH_KSTEP(kt, 2, 0, 0, 0, false, false)
-#undef PH_KSTEP
-  // both wave rows run the epilogue together (row 0 waits out row 1's last phase)
-  if (wr == 0) __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");  // the epilogue's LDS slot writes stay behind that barrier
-  const int mw = m0 + wr * TM, nw = n0 + wc * TN;
-  const float* lbp = (const float*)(smem + 2 * STAGE) - n0;  // staged bias, by column
-  // the epilogue's per-wave 4-KiB LDS slot: regions A1 / B1 of the last K-step's stage,
-  // whose last reads (P3 / P2) every wave finished before the barrier above (no DMA is
-  // issued after the last K-step's regions)
-  char* slot = smem + ((nk - 1) & 1) * STAGE + (wr ? 3 : 1) * REGION + wc * 4096;
-  if (stamp) ts[1] = __builtin_amdgcn_s_memtime();
-  if (a.dbg & 1) {
-#pragma unroll
-    for (int i = 0; i < RM; ++i)
-#pragma unroll
-      for (int j = 0; j < RN; ++j) asm volatile("" ::"v"(acc[i][j]));
-  } else if constexpr (SCORES) {  // seg/det proj -> map partials
-    if (key == AACLIP_EPI_LEAKY)
-      wave_epilogue<RM, RN, 3, AACLIP_EPI_LEAKY, 0, H16>(a, acc, mw, nw, lane);
-    else
-      wave_epilogue<RM, RN, 3, 0, 0, H16>(a, acc, mw, nw, lane);
-  } else {
-#define EPI_CASE(BF, E)                                                                          \
-  if (bf16_out == (BF) && key == (E)) {                                                          \
-    wave_epilogue_lds<RM, RN, BF ? 1 : 0, E, H16>(a, acc, mw, nw, lane,                          \
-                                                  ((E) & AACLIP_EPI_BIAS) ? lbp : nullptr, slot); \
-  } else
-    EPI_CASE(true, AACLIP_EPI_BIAS)
-    EPI_CASE(true, AACLIP_EPI_BIAS | AACLIP_EPI_GELU)
-    EPI_CASE(true, AACLIP_EPI_BIAS | AACLIP_EPI_QGELU)
-    EPI_CASE(false, AACLIP_EPI_BIAS | AACLIP_EPI_RESID)
-    EPI_CASE(false, AACLIP_EPI_BIAS | AACLIP_EPI_RESID | AACLIP_EPI_AUX_BF16)
-    EPI_CASE(false, AACLIP_EPI_LEAKY)
-#undef EPI_CASE
-    // any other flag combination (row remap, 16-bit rows + residual, ...): run-time flags
-    if (bf16_out)
-      wave_epilogue_lds<RM, RN, 1, -1, H16>(a, acc, mw, nw, lane, lds_bias ? lbp : nullptr, slot);
-    else
-      wave_epilogue_lds<RM, RN, 0, -1, H16>(a, acc, mw, nw, lane, lds_bias ? lbp : nullptr, slot);
-  }
-#undef PH_SYNC_MFMA
-#undef PHASE_STAMP_A
-#undef PHASE_STAMP_B
-#undef PHASE_STAMP_STORE
-  if (stamp) ts[2] = __builtin_amdgcn_s_memtime();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every load / store retired before exit
-  if (stamp) {
-    ts[3] = __builtin_amdgcn_s_memtime();
-#ifdef AACLIP_PHASE_STAMPS
-    if (lane < 2 * 4 * kPSN) ((uint64_t*)a.aux)[((size_t)blockIdx.x * 8 + wid) * 2 * 4 * kPSN + lane] = ps_lds[lane];
-#else
-    if (lane < 4) ((uint64_t*)a.aux)[((size_t)blockIdx.x * 8 + wid) * 4 + lane] = ts[lane];
-#endif
-  }
-}
-
-// ============================ 8-phase ping-pong fp8 MX kernel (256x256, K-step 128)
-// The bf16 8-phase schedule above on e4m3 operands: a 128-byte LDS row is one
-// 128-K step, each phase is 4x2 K=128 MFMAs (256 cycles, as 16 bf16 MFMAs), and the
-// A tile's e8m0 block scales (512 B per K-step) ride in a 3-slot LDS ring issued in
-// P3 with region A0: every wave issues one dword LDS-DMA there (waves 0-1 carry the
-// 512 B, waves 2-7 write a scratch area nobody reads) so the per-phase DMA counts
-// (2, 2, 3, 2) are uniform and any 4 consecutive phases hold 9 -> vmcnt(9). Slot
-// (k+2)%3 is rewritten at P3(k), 4 phases after K-step k-1's last scale read.
-__global__ __launch_bounds__(512) void gemm_fp8mx_8ph_kernel(GemmArgs a) {
-  AACLIP_TRACE_SCOPE(TR_GEMM_FP8MX | gemm_trace_tag(a));
-  constexpr int BM = 256, BN = 256, TM = 128, TN = 64, RM = 8, RN = 4;
-  constexpr int REGION = 128 * 128;
-  constexpr int STAGE = 4 * REGION;
-  constexpr int SCB = 2 * STAGE, SC_SLOT = 512;  // 3 scale slots, then 6 x 256 B scratch
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int t = threadIdx.x;
-  const int lane = t & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wr = wid >> 2, wc = wid & 3;
-  const int fr = lane & 15, fq = lane >> 4;
-  int tm, tn;
-  tile_coords(blockIdx.x, a.tiles_m, a.tiles_n, tm, tn, a.group_m);
-  const int m0 = tm * BM, n0 = tn * BN;
-  const auto ars = __builtin_amdgcn_make_buffer_rsrc((void*)a.A, 0, (int)((uint32_t)a.M * (uint32_t)a.lda),
-                                                     0x00020000);
-  const auto wrs = __builtin_amdgcn_make_buffer_rsrc((void*)a.W, 0, (int)((uint32_t)a.N * (uint32_t)a.ldw),
-                                                     0x00020000);
-  const auto srs =
-      __builtin_amdgcn_make_buffer_rsrc((void*)a.a_mx, 0, (int)((a.K / 128) * a.ld_amx * 2), 0x00020000);
-  const int prow = t >> 3;
-  const int pchunk = ((t & 7) ^ (prow & 7)) * 16;
-  const int a_vo = (m0 + prow) * (int)a.lda + pchunk;
-  const int w_vo = (n0 + ((prow >> 5) & 1) * 64 + (prow & 31)) * (int)a.ldw + pchunk;
-  const int a_row = (int)a.lda, w_row = (int)a.ldw;
-  const int nk = a.K / 128;
-  auto issue = [&](int r, int kt) {
-    const int kc = kt * 128;
-    char* dst = smem + (kt & 1) * STAGE + r * REGION;
-#pragma unroll
-    for (int g = 0; g < 2; ++g) {
-      if (r < 2)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ars, LDS_PTR(dst + g * 8192 + wid * 1024), 16, a_vo,
-                                                 (g * 128 + r * 64) * a_row + kc, 0, 0);
-      else
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, LDS_PTR(dst + g * 8192 + wid * 1024), 16, w_vo,
-                                                 (g * 128 + (r - 2) * 32) * w_row + kc, 0, 0);
-    }
-  };
-  // scale slot of K-step kt is kt % 3; waves 2..7 park their (unused) DMA lanes in
+  // MX: the scale slot of K-step kt is kt % 3; waves 2..7 park their (unused) DMA lanes in
   // scratch. Branch-free on purpose: a branch here splits the loop body into two
   // blocks and the (memory-free) MFMAs then get sunk across the phase barriers.
   auto issue_sc = [&](int kt, int slot) {
@@ -1077,6 +875,8 @@ __global__ __launch_bounds__(512) void gemm_fp8mx_8ph_kernel(GemmArgs a) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(srs, LDS_PTR(dst), 4, m0 * 2 + (wid & 1) * 256 + lane * 4,
                                              (int)(kc * a.ld_amx * 2), 0, 0);
   };
+  // fragment offsets inside a region: local row (A: wr*64 + 16i + fr, B: wc*32 + 16j + fr),
+  // 16-B chunk (kk*4 + fq) ^ (fr & 7); an fp8 fragment is chunks fq and 4 + fq (gemm_bf16_kernel)
   int a_rd[2], b_rd[2];
 #pragma unroll
   for (int kk = 0; kk < 2; ++kk) {
@@ -1085,159 +885,249 @@ __global__ __launch_bounds__(512) void gemm_fp8mx_8ph_kernel(GemmArgs a) {
     b_rd[kk] = 2 * REGION + (wc * 32 + fr) * 128 + sw;
   }
   float4_t acc[RM][RN];
-#pragma unroll
-  for (int i = 0; i < RM; ++i)
-#pragma unroll
-    for (int j = 0; j < RN; ++j) acc[i][j] = float4_t{0.f, 0.f, 0.f, 0.f};
-  i32x8_t af[4], bfr[2][2];
-  int sa[4];
+  Frag af[4][KK], bfr[2][2][KK];  // A sub-block (4 tiles x kk), B sub-blocks [q][j][kk]
+  [[maybe_unused]] int sa[4];     // MX: the A sub-block's e8m0 scales
+  [[maybe_unused]] int sc_cur = 0, sc_next = 2;  // MX: scale slots kt % 3, (kt + 2) % 3
 
-  // prologue = the steady state's P3(-2), P4(-2), P1(-1), P2(-1), P3(-1), P4(-1) issues
+  // 16-bit: the tile's 256 bias values into LDS behind the ring (one 1-KiB DMA by wave 0, retired by
+  // the prologue's vmcnt(8) as the oldest op): the epilogue reads them from LDS instead of
+  // waiting out a global-load round trip at its start
+  const bool lds_bias = !MX && !SCORES && (a.epi & AACLIP_EPI_BIAS);
+  if (lds_bias && wid == 0) {
+    const auto brs = __builtin_amdgcn_make_buffer_rsrc((void*)a.bias, 0, (int)((uint32_t)a.N * 4u), 0x00020000);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(brs, LDS_PTR(smem + 2 * STAGE), 16, (tn * BN + 4 * lane) * 4, 0, 0, 0);
+  }
+  // prologue: all of K-step 0, then A0 / B0 of K-step 1 (the steady state's P3/P4 of K-steps -2, -1)
   issue(0, 0);
-  issue_sc(0, 0);
+  if constexpr (MX) issue_sc(0, 0);
   issue(2, 0);
   issue(3, 0);
   issue(1, 0);
   if (nk > 1) {
     issue(0, 1);
-    issue_sc(1, 1);
+    if constexpr (MX) issue_sc(1, 1);
     issue(2, 1);
-    asm volatile("s_waitcnt vmcnt(9)" ::: "memory");  // A0(0), SC(0), B0(0) landed
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAIT) : "memory");  // A0(0), SC(0), B0(0) landed
   } else {
     asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // one K-step: B1(0), A1(0) may fly
   }
   __builtin_amdgcn_s_barrier();
-  if (wr == 1) __builtin_amdgcn_s_barrier();
-
-  auto frag = [&](const char* p0, const char* p1) {
-    const i32x4_t lo = *(const i32x4_t*)p0, hi = *(const i32x4_t*)p1;
-    return i32x8_t{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+  if (wr == 1) __builtin_amdgcn_s_barrier();  // stagger: wave row 1 runs one barrier behind
+  // 16-bit: no s_setprio flips around the MFMA clusters (the sched_barrier fences already pin each
+  // cluster between its barriers): C2 step +0.8 % over setprio 1/0 around every cluster;
+  // a static prio 1 for the younger wave row measured the same as none, keeping the flips
+  // for the older row -2.5 % (profiles/r04/gemm_8ph_priority_ab.txt). The MX kernel keeps them.
+  auto mfma_q = [&](int qa, int qb) {
+    if constexpr (MX) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int kk = 0; kk < KK; ++kk)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          float4_t& c = acc[qa * 4 + i][qb * 2 + j];
+          if constexpr (MX)  // formats 0/0 = e4m3/e4m3; W block scale 2^0, A block scale sa
+            c = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(bfr[qb][j][kk], af[i][kk], c, 0, 0, 0, 127, 0, sa[i]);
+          else
+            c = mfma16(bfr[qb][j][kk], af[i][kk], c);
+        }
+    if constexpr (MX) __builtin_amdgcn_s_setprio(0);
   };
-  auto read_a = [&](const char* st, int q, int slot) {
+  // one fragment of the row at p: 16-bit, its k-half kk; fp8, both of its 16-byte chunks
+  auto frag = [&](const char* p, const int (&rd)[2], int kk) {
+    if constexpr (MX) {
+      const i32x4_t lo = *(const i32x4_t*)(p + rd[0]), hi = *(const i32x4_t*)(p + rd[1]);
+      return i32x8_t{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    } else {
+      return *(const Frag*)(p + rd[kk]);
+    }
+  };
+  auto read_a = [&](const char* st, int q) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      af[i] = frag(st + q * REGION + a_rd[0] + i * 2048, st + q * REGION + a_rd[1] + i * 2048);
-      sa[i] = *(const uint8_t*)(smem + SCB + slot * SC_SLOT + (wr * 128 + q * 64 + 16 * i + fr) * 2 + (fq >> 1));
+#pragma unroll
+      for (int kk = 0; kk < KK; ++kk) af[i][kk] = frag(st + q * REGION + i * 2048, a_rd, kk);
+      if constexpr (MX)
+        sa[i] = *(const uint8_t*)(smem + SCB + sc_cur * SC_SLOT + (wr * 128 + q * 64 + 16 * i + fr) * 2 + (fq >> 1));
     }
   };
   auto read_b = [&](const char* st, int q) {
 #pragma unroll
     for (int j = 0; j < 2; ++j)
-      bfr[q][j] = frag(st + q * REGION + b_rd[0] + j * 2048, st + q * REGION + b_rd[1] + j * 2048);
-  };
-  auto mfma_q = [&](int qa, int qb) {
-    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        acc[qa * 4 + i][qb * 2 + j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-            bfr[qb][j], af[i], acc[qa * 4 + i][qb * 2 + j], 0, 0, 0, 127, 0, sa[i]);
-    __builtin_amdgcn_s_setprio(0);
+      for (int kk = 0; kk < KK; ++kk) bfr[q][j][kk] = frag(st + q * REGION + j * 2048, b_rd, kk);
   };
-#define PH_SYNC_MFMA(QA, QB, W)                              \
-  asm volatile("s_waitcnt vmcnt(" #W ")" ::: "memory");      \
-  __builtin_amdgcn_s_barrier();                              \
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");         \
-  __builtin_amdgcn_sched_barrier(0);                         \
-  mfma_q(QA, QB);                                            \
-  __builtin_amdgcn_sched_barrier(0);                         \
-  __builtin_amdgcn_s_barrier();
+#define PH_SYNC_MFMA(QA, QB, W)                                \
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W) : "memory");     \
+  __builtin_amdgcn_s_barrier();                                \
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           \
+  PHASE_STAMP_A                                                \
+  __builtin_amdgcn_sched_barrier(0);                           \
+  mfma_q(QA, QB);                                              \
+  __builtin_amdgcn_sched_barrier(0);                           \
+  PHASE_STAMP_B                                                \
+  __builtin_amdgcn_s_barrier();                                \
+  PHASE_STAMP_STORE
 
-  int slot = 0, slot2 = 2;  // kt % 3, (kt + 2) % 3
-  // one K-step with its four counted waits; I1 / I2: it issues K-step kt+1's / kt+2's
-  // regions (compile-time constants at every use: no branch splits the body)
-#define MX_KSTEP(KT, W1, W2, W3, W4, I1, I2)        \
-  {                                                 \
-    const char* st = smem + ((KT) & 1) * STAGE;     \
-    read_b(st, 0); /* P1: A0 x B0 */                \
-    read_a(st, 0, slot);                            \
-    if (I1) issue(3, (KT) + 1);                     \
-    PH_SYNC_MFMA(0, 0, W1)                          \
-    read_b(st, 1); /* P2: A0 x B1 */                \
-    if (I1) issue(1, (KT) + 1);                     \
-    PH_SYNC_MFMA(0, 1, W2)                          \
-    read_a(st, 1, slot); /* P3: A1 x B1 */          \
-    if (I2) {                                       \
-      issue(0, (KT) + 2);                           \
-      issue_sc((KT) + 2, slot2);                    \
-    }                                               \
-    PH_SYNC_MFMA(1, 1, W3)                          \
-    if (I2) issue(2, (KT) + 2); /* P4: A1 x B0 */   \
-    PH_SYNC_MFMA(1, 0, W4)                          \
-    slot = slot == 2 ? 0 : slot + 1;                \
-    slot2 = slot2 == 2 ? 0 : slot2 + 1;             \
+  // diagnostic stamps (16-bit, variant bit 11): shader-clock s_memtime at kernel start, main-loop
+  // end, epilogue issued, epilogue stores complete -> a.aux
+  const bool stamp = !MX && (a.dbg & 4) && a.aux && !(a.epi & AACLIP_EPI_AUX_BF16);
+#ifdef AACLIP_PHASE_STAMPS
+  uint64_t* const ps_lds = (uint64_t*)(smem + 2 * STAGE + 1024) + wid * kPSN * 4 * 2;
+  [[maybe_unused]] int ps_i = 0;  // phase index since kernel start
+  [[maybe_unused]] uint64_t ps_a = 0, ps_b = 0;
+#endif
+  uint64_t ts[4] = {0, 0, 0, 0};
+  if (stamp) ts[0] = __builtin_amdgcn_s_memtime();
+#pragma unroll
+  for (int i = 0; i < RM; ++i)
+#pragma unroll
+    for (int j = 0; j < RN; ++j) acc[i][j] = float4_t{0.f, 0.f, 0.f, 0.f};
+  // One K-step: P1 A0 x B0, P2 A0 x B1, P3 A1 x B1, P4 A1 x B0, each phase's counted wait
+  // W1..W4; I1 / I2: the K-step issues its regions of K-steps kt+1 / kt+2 (compile-time
+  // constants at every use: no branch splits the body).
+#define PH_KSTEP(KT, W1, W2, W3, W4, I1, I2)           \
+  {                                                    \
+    const char* st = smem + ((KT) & 1) * STAGE;        \
+    read_b(st, 0);                                     \
+    read_a(st, 0);                                     \
+    if (I1) issue(3, (KT) + 1);                        \
+    PH_SYNC_MFMA(0, 0, W1)                             \
+    read_b(st, 1);                                     \
+    if (I1) issue(1, (KT) + 1);                        \
+    PH_SYNC_MFMA(0, 1, W2)                             \
+    read_a(st, 1);                                     \
+    if (I2) {                                          \
+      issue(0, (KT) + 2);                              \
+      if constexpr (MX) issue_sc((KT) + 2, sc_next);   \
+    }                                                  \
+    PH_SYNC_MFMA(1, 1, W3)                             \
+    if (I2) issue(2, (KT) + 2);                        \
+    PH_SYNC_MFMA(1, 0, W4)                             \
+    if constexpr (MX) {                                \
+      sc_cur = sc_cur == 2 ? 0 : sc_cur + 1;           \
+      sc_next = sc_next == 2 ? 0 : sc_next + 1;        \
+    }                                                  \
   }
   int kt = 0;
-  for (; kt < nk - 2; ++kt) MX_KSTEP(kt, 9, 9, 9, 9, true, true)
-  // the last two K-steps issue nothing past the end (as the bf16 kernel): P4 of K-step nk-2
-  // leaves B1 / A1 of nk-1 in flight (vmcnt 4), P1 of nk-1 only A1 (2), P2 drains
+  for (; kt < nk - 2; ++kt) PH_KSTEP(kt, WAIT, WAIT, WAIT, WAIT, true, true)
+  // The last two K-steps issue nothing past the last K-step: in K-step nk-2 P3 / P4 issue
+  // nothing, so P4 waits for A0 / B0 of nk-1 with only B1 / A1 of nk-1 left in flight
+  // (vmcnt 4); in K-step nk-1 P1 leaves A1 (vmcnt 2) and P2 drains. (Until round 5 the
+  // steady-state body ran to the end with phantom re-reads of the last K-step -- 1.5 K-steps
+  // of DMA per tile nobody read, still in flight ahead of the epilogue's own loads.)
   if (nk >= 2) {
-    MX_KSTEP(kt, 9, 9, 9, 4, true, false)
+    PH_KSTEP(kt, WAIT, WAIT, WAIT, 4, true, false)
     ++kt;
   }
-  MX_KSTEP(kt, 2, 0, 0, 0, false, false)
-#undef MX_KSTEP
+  PH_KSTEP(kt, 2, 0, 0, 0, false, false)
+#undef PH_KSTEP
 #undef PH_SYNC_MFMA
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  if constexpr (MX) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  // both wave rows run the epilogue together (row 0 waits out row 1's last phase)
   if (wr == 0) __builtin_amdgcn_s_barrier();
-  if (a.dbg & 1) {  // diagnostic timing path (variant bit 9): keep the MFMA results live, store nothing
+  auto keep_acc = [&] {  // diagnostic timing path (variant bit 9): keep the MFMA results live, store nothing
 #pragma unroll
     for (int i = 0; i < RM; ++i)
 #pragma unroll
       for (int j = 0; j < RN; ++j) asm volatile("" ::"v"(acc[i][j]));
-    return;
+  };
+  if constexpr (MX) {
+    if (a.dbg & 1) {
+      keep_acc();
+      return;
+    }
   }
   asm volatile("" ::: "memory");  // the epilogue's LDS slot writes stay behind that barrier
   const int mw = m0 + wr * TM, nw = n0 + wc * TN;
-  const int key = a.epi;
-  const int outm = a.out_dtype == AACLIP_F32 ? 0 : (a.out_dtype == AACLIP_BF16 ? 1 : 2);
-  // quad-coalesced epilogue through the same per-wave LDS slot as the bf16 8-phase
-  // kernel (A1 / B1 of the last K-step's stage: no DMA lands there after their last reads)
-  char* eslot = smem + ((nk - 1) & 1) * STAGE + (wr ? 3 : 1) * REGION + wc * 4096;
-#define EPI_CASE(OM, E)                                                         \
-  if (outm == (OM) && key == (E)) {                                             \
-    wave_epilogue_lds<RM, RN, OM, E, false, 2>(a, acc, mw, nw, lane, nullptr, eslot); \
-    return;                                                                     \
+  // the epilogue's per-wave 4-KiB LDS slot: regions A1 / B1 of the last K-step's stage,
+  // whose last reads (P3 / P2) every wave finished before the barrier above (no DMA is
+  // issued after the last K-step's regions)
+  char* slot = smem + ((nk - 1) & 1) * STAGE + (wr ? 3 : 1) * REGION + wc * 4096;
+  if constexpr (MX) {
+    const int key = a.epi;  // the MX entry takes no row remap
+    const int outm = a.out_dtype == AACLIP_F32 ? 0 : (a.out_dtype == AACLIP_BF16 ? 1 : 2);
+#define EPI_CASE(OM, E)                                                              \
+  if (outm == (OM) && key == (E)) {                                                  \
+    wave_epilogue_lds<RM, RN, OM, E, false, 2>(a, acc, mw, nw, lane, nullptr, slot); \
+    return;                                                                          \
   }
-  EPI_CASE(1, AACLIP_EPI_BIAS)                                          // qkv
-  EPI_CASE(0, AACLIP_EPI_BIAS | AACLIP_EPI_RESID)                       // out-proj, c_proj
-  EPI_CASE(0, AACLIP_EPI_BIAS | AACLIP_EPI_RESID | AACLIP_EPI_AUX_BF16)  // c_proj + bf16 copy
-  EPI_CASE(2, AACLIP_EPI_BIAS | AACLIP_EPI_GELU)                        // c_fc -> fp8 MX
-  EPI_CASE(2, AACLIP_EPI_BIAS | AACLIP_EPI_QGELU)
+    EPI_CASE(1, AACLIP_EPI_BIAS)                                          // qkv
+    EPI_CASE(0, AACLIP_EPI_BIAS | AACLIP_EPI_RESID)                       // out-proj, c_proj
+    EPI_CASE(0, AACLIP_EPI_BIAS | AACLIP_EPI_RESID | AACLIP_EPI_AUX_BF16)  // c_proj + bf16 copy
+    EPI_CASE(2, AACLIP_EPI_BIAS | AACLIP_EPI_GELU)                        // c_fc -> fp8 MX
+    EPI_CASE(2, AACLIP_EPI_BIAS | AACLIP_EPI_QGELU)
 #undef EPI_CASE
-  if (outm == 1)
-    wave_epilogue<RM, RN, 1, -1, 2>(a, acc, mw, nw, lane);
-  else if (outm == 0)
-    wave_epilogue<RM, RN, 0, -1, 2>(a, acc, mw, nw, lane);
+    if (outm == 1)
+      wave_epilogue<RM, RN, 1, -1, 2>(a, acc, mw, nw, lane);
+    else if (outm == 0)
+      wave_epilogue<RM, RN, 0, -1, 2>(a, acc, mw, nw, lane);
+  } else {
+    const bool bf16_out = a.out_dtype != AACLIP_F32;
+    const int key = a.epi | (a.row_group > 0 ? EPI_REMAP : 0);
+    const float* lbp = (const float*)(smem + 2 * STAGE) - n0;  // staged bias, by column
+    if (stamp) ts[1] = __builtin_amdgcn_s_memtime();
+    if (a.dbg & 1) {
+      keep_acc();
+    } else if constexpr (SCORES) {  // seg/det proj -> map partials
+      if (key == AACLIP_EPI_LEAKY)
+        wave_epilogue<RM, RN, 3, AACLIP_EPI_LEAKY, 0, H16>(a, acc, mw, nw, lane);
+      else
+        wave_epilogue<RM, RN, 3, 0, 0, H16>(a, acc, mw, nw, lane);
+    } else {
+#define EPI_CASE(BF, E)                                                                          \
+  if (bf16_out == (BF) && key == (E)) {                                                          \
+    wave_epilogue_lds<RM, RN, BF ? 1 : 0, E, H16>(a, acc, mw, nw, lane,                          \
+                                                  ((E) & AACLIP_EPI_BIAS) ? lbp : nullptr, slot); \
+  } else
+      EPI_CASE(true, AACLIP_EPI_BIAS)
+      EPI_CASE(true, AACLIP_EPI_BIAS | AACLIP_EPI_GELU)
+      EPI_CASE(true, AACLIP_EPI_BIAS | AACLIP_EPI_QGELU)
+      EPI_CASE(false, AACLIP_EPI_BIAS | AACLIP_EPI_RESID)
+      EPI_CASE(false, AACLIP_EPI_BIAS | AACLIP_EPI_RESID | AACLIP_EPI_AUX_BF16)
+      EPI_CASE(false, AACLIP_EPI_LEAKY)
+#undef EPI_CASE
+      // any other flag combination (row remap, 16-bit rows + residual, ...): run-time flags
+      if (bf16_out)
+        wave_epilogue_lds<RM, RN, 1, -1, H16>(a, acc, mw, nw, lane, lds_bias ? lbp : nullptr, slot);
+      else
+        wave_epilogue_lds<RM, RN, 0, -1, H16>(a, acc, mw, nw, lane, lds_bias ? lbp : nullptr, slot);
+    }
+    if (stamp) ts[2] = __builtin_amdgcn_s_memtime();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every load / store retired before exit
+    if (stamp) {
+      ts[3] = __builtin_amdgcn_s_memtime();
+#ifdef AACLIP_PHASE_STAMPS
+      if (lane < 2 * 4 * kPSN) ((uint64_t*)a.aux)[((size_t)blockIdx.x * 8 + wid) * 2 * 4 * kPSN + lane] = ps_lds[lane];
+#else
+      if (lane < 4) ((uint64_t*)a.aux)[((size_t)blockIdx.x * 8 + wid) * 4 + lane] = ts[lane];
+#endif
+    }
+  }
 }
+#undef PHASE_STAMP_A
+#undef PHASE_STAMP_B
+#undef PHASE_STAMP_STORE
 
-int launch_fp8mx_8ph(GemmArgs a, hipStream_t s) {
+// LDS of a launch: the two-stage tile ring, then the tile's staged bias (16-bit; + the phase
+// stamps in the diagnostic build) or the 3 scale slots and 6 x 256 B of scratch (MX)
+template <int Q, bool H16, bool SCORES>
+int launch_8ph(GemmArgs a, hipStream_t s) {
+  if (a.N % 256 || a.K % (Q ? 128 : 64)) return AACLIP_ERR_ARG;
   a.tiles_m = ceil_div(a.M, 256);
   a.tiles_n = a.N / 256;
-  const size_t lds = 2 * 4 * 128 * 128 + 3 * 512 + 6 * 256;
+  size_t lds = 2 * 4 * 128 * 128 + (Q ? 3 * 512 + 6 * 256 : 1024);
+#ifdef AACLIP_PHASE_STAMPS
+  if (!Q) lds += 8 * 8 * 4 * 2 * 8;
+#endif
   static unsigned attr_dev = 0;
-  if (!lds_attr_once((const void*)gemm_fp8mx_8ph_kernel, (int)lds, attr_dev)) return AACLIP_ERR_LAUNCH;
-  gemm_fp8mx_8ph_kernel<<<a.tiles_m * a.tiles_n, 512, lds, s>>>(a);
+  if (!lds_attr_once((const void*)gemm_8ph_kernel<Q, H16, SCORES>, (int)lds, attr_dev)) return AACLIP_ERR_LAUNCH;
+  gemm_8ph_kernel<Q, H16, SCORES><<<a.tiles_m * a.tiles_n, 512, lds, s>>>(a);
   AACLIP_CHECK_LAUNCH();
   return AACLIP_OK;
 }
 
 int cu_count();
-
-template <bool H16, bool SCORES = false>
-int launch_bf16_8ph(GemmArgs a, hipStream_t s) {
-  if (a.N % 256 || a.K % 64) return AACLIP_ERR_ARG;
-  a.tiles_m = ceil_div(a.M, 256);
-  a.tiles_n = a.N / 256;
-  const size_t lds = k8phLdsBytes;
-  static unsigned attr_dev = 0;
-  if (!lds_attr_once((const void*)gemm_bf16_8ph_kernel<H16, SCORES>, (int)lds, attr_dev))
-    return AACLIP_ERR_LAUNCH;
-  gemm_bf16_8ph_kernel<H16, SCORES><<<a.tiles_m * a.tiles_n, 512, lds, s>>>(a);
-  AACLIP_CHECK_LAUNCH();
-  return AACLIP_OK;
-}
 
 template <int BM, int BN, int WM, int WN, int Q = 0, bool H16 = false>
 int launch_bf16(GemmArgs a, hipStream_t s) {
@@ -1363,8 +1253,9 @@ int choose16(int dtype, int M, int N, int K, bool fits) {
   return N % 256 == 0 ? KERN_320x256 : KERN_256x128;
 }
 
-// 16-bit dispatch (bf16 or fp16 operands; same tiles, same per-shape choice)
-template <bool H16>
+// 16-bit dispatch (bf16 or fp16 operands; same tiles, same per-shape choice, so the same K order
+// and the same bits). SCORES: the launch of aaclip_gemm_scores (score-partials epilogue).
+template <bool H16, bool SCORES>
 int dispatch16(GemmArgs a, hipStream_t s) {
   const int M = a.M, N = a.N;
   if (a.K % 64 || N % 128) return AACLIP_ERR_ARG;
@@ -1374,12 +1265,35 @@ int dispatch16(GemmArgs a, hipStream_t s) {
                     !(a.out_dtype != AACLIP_F32 && (a.epi & AACLIP_EPI_AUX_BF16));
   switch (choose16(H16 ? AACLIP_F16 : AACLIP_BF16, M, N, a.K, fits)) {
     case KERN_256x256: return launch_bf16<256, 256, 2, 4, 0, H16>(a, s);
-    case KERN_8PH: return launch_bf16_8ph<H16>(a, s);
+    case KERN_8PH:  // scores: "8-phase but does not fit" falls to 320x256
+      if (SCORES && !fits) return launch_bf16<320, 256, 2, 4, 0, H16>(a, s);
+      return launch_8ph<0, H16, SCORES>(a, s);
     case KERN_320x256: return launch_bf16<320, 256, 2, 4, 0, H16>(a, s);
     case KERN_128x128: return launch_bf16<128, 128, 2, 2, 0, H16>(a, s);
     case KERN_64x64: return launch_bf16<64, 64, 2, 2, 0, H16>(a, s);
     default: return launch_bf16<256, 128, 4, 2, 0, H16>(a, s);
   }
+}
+
+// The epilogue-argument rules aaclip_gemm, aaclip_gemm_fp8 and aaclip_gemm_fp8mx share. aux_ld_multiple: the aux copy's rows leave as
+// 16-byte stores beside 16-bit operands (ld % 8 elements), as 8-byte ones beside fp8 (ld % 4).
+bool check_epilogue_args(int epilogue, const float* bias, const float* residual, int64_t ldr, const void* aux,
+                         int64_t ldaux, int N, int aux_ld_multiple) {
+  if ((epilogue & AACLIP_EPI_BIAS) && (!bias || ((uintptr_t)bias % 16) != 0)) return false;
+  if ((epilogue & AACLIP_EPI_RESID) && !(residual && ldr >= N && ldr % 4 == 0)) return false;
+  if ((epilogue & AACLIP_EPI_AUX_BF16) && !(aux && ldaux >= N && ldaux % aux_ld_multiple == 0)) return false;
+  return (epilogue & ~63) == 0 &&
+         (epilogue & (AACLIP_EPI_GELU | AACLIP_EPI_QGELU)) != (AACLIP_EPI_GELU | AACLIP_EPI_QGELU);
+}
+
+// The fields every entry fills the same way; the rest start at zero and are assigned by name.
+GemmArgs gemm_args(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int M, int N, int K,
+                   int epilogue, int out_dtype) {
+  GemmArgs a{};
+  a.A = A, a.lda = lda, a.W = W, a.ldw = ldw, a.C = C, a.ldc = ldc;
+  a.M = M, a.N = N, a.K = K, a.epi = epilogue, a.out_dtype = out_dtype;
+  a.group_m = g_group_m, a.setprio = g_setprio;
+  return a;
 }
 
 }  // namespace
@@ -1390,7 +1304,7 @@ extern "C" const char* aaclip_gemm_plan(int in_dtype, int M, int N, int K) {
   if (in_dtype != AACLIP_BF16 && in_dtype != AACLIP_F16) return "gemm_f32_kernel";
   if (M <= 0 || N % 128 || K % 64) return "invalid";
   const bool fits = (int64_t)M * K * 2 < (1ll << 31) && (int64_t)N * K * 2 < (1ll << 31);
-  switch (choose16(in_dtype, M, N, K, fits)) {
+  switch (choose16(in_dtype, M, N, K, fits)) {  // bench.py and the profile tools key on these strings
     case KERN_256x256: return "gemm_bf16_kernel<256,256,2,4>";
     case KERN_8PH: return "gemm_bf16_8ph_kernel<256,256>";
     case KERN_320x256: return "gemm_bf16_kernel<320,256,2,4>";
@@ -1464,12 +1378,7 @@ extern "C" int aaclip_gemm(int in_dtype, int out_dtype, int M, int N, int K, con
   AACLIP_REQUIRE(lda >= K && ldw >= K && ldc >= N && lda % 8 == 0 && ldw % 8 == 0 &&
                  ldc % (out_dtype == AACLIP_F32 ? 4 : 8) == 0);
   AACLIP_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)C % 16) == 0);
-  AACLIP_REQUIRE(!(epilogue & AACLIP_EPI_BIAS) || bias);
-  AACLIP_REQUIRE(!(epilogue & AACLIP_EPI_BIAS) || ((uintptr_t)bias % 16) == 0);
-  AACLIP_REQUIRE(!(epilogue & AACLIP_EPI_RESID) || (residual && ldr >= N && ldr % 4 == 0));
-  AACLIP_REQUIRE(!(epilogue & AACLIP_EPI_AUX_BF16) || (aux && ldaux >= N && ldaux % 8 == 0));
-  AACLIP_REQUIRE((epilogue & ~63) == 0 && (epilogue & (AACLIP_EPI_GELU | AACLIP_EPI_QGELU)) !=
-                                               (AACLIP_EPI_GELU | AACLIP_EPI_QGELU));
+  AACLIP_REQUIRE(check_epilogue_args(epilogue, bias, residual, ldr, aux, ldaux, N, 8));
   AACLIP_REQUIRE(row_group >= 0 && (row_group == 0 || row_group_out >= row_group));
   // the shape rules hold for an empty batch too (M == 0 is accepted only where M > 0 would be)
   if (in_dtype == AACLIP_F32)
@@ -1477,12 +1386,13 @@ extern "C" int aaclip_gemm(int in_dtype, int out_dtype, int M, int N, int K, con
   else
     AACLIP_REQUIRE(K % 64 == 0 && N % 128 == 0);
   if (M == 0) return AACLIP_OK;
-  GemmArgs a{A, W, C, bias, residual, aux, lda, ldw, ldc, ldr, ldaux, M, N, K, epilogue,
-             out_dtype, row_group, row_group_out, row_offset, 0, 0, g_group_m, g_setprio, g_dbg,
-             nullptr, nullptr, nullptr, 0, nullptr, 0};
+  GemmArgs a = gemm_args(A, lda, W, ldw, C, ldc, M, N, K, epilogue, out_dtype);
+  a.bias = bias, a.res = residual, a.ldr = ldr, a.aux = aux, a.ldaux = ldaux;
+  a.row_group = row_group, a.row_group_out = row_group_out, a.row_offset = row_offset;
+  a.dbg = g_dbg;
   hipStream_t s = (hipStream_t)stream;
-  if (in_dtype == AACLIP_BF16) return dispatch16<false>(a, s);
-  if (in_dtype == AACLIP_F16) return dispatch16<true>(a, s);
+  if (in_dtype == AACLIP_BF16) return dispatch16<false, false>(a, s);
+  if (in_dtype == AACLIP_F16) return dispatch16<true, false>(a, s);
   a.tiles_m = ceil_div(M, 64);
   a.tiles_n = N / 64;
   gemm_f32_kernel<<<a.tiles_m * a.tiles_n, 256, 0, s>>>(a);
@@ -1499,30 +1409,14 @@ extern "C" int aaclip_gemm_scores(int in_dtype, int M, int N, int K, const void*
   AACLIP_REQUIRE(lda >= K && ldw >= K && lda % 8 == 0 && ldw % 8 == 0);
   AACLIP_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)part % 16) == 0 &&
                  ((uintptr_t)T % 16) == 0);
-  AACLIP_REQUIRE(epilogue == 0 || epilogue == AACLIP_EPI_LEAKY);
+  AACLIP_REQUIRE(epilogue == 0 || epilogue == AACLIP_EPI_LEAKY);  // no bias, residual or aux: nothing more to check
   if (M == 0) return AACLIP_OK;
-  GemmArgs a{A, W, part, nullptr, nullptr, nullptr, lda, ldw, ld_part, 0, 0, M, N, K, epilogue,
-             kOutScores, 0, 0, 0, 0, 0, g_group_m, g_setprio, g_dbg & 1,
-             nullptr, nullptr, nullptr, 0, nullptr, 0, T, t_period};
-  hipStream_t s = (hipStream_t)stream;
-  const bool h16 = in_dtype == AACLIP_F16;
-  const bool fits = (int64_t)M * lda * 2 < (1ll << 31) && (int64_t)N * ldw * 2 < (1ll << 31);
+  GemmArgs a = gemm_args(A, lda, W, ldw, part, ld_part, M, N, K, epilogue, kOutScores);
+  a.dbg = g_dbg & 1;
+  a.anchors = T, a.t_period = t_period;
   // the same per-shape choice as aaclip_gemm (same K order, same bits)
-  switch (choose16(in_dtype, M, N, K, fits)) {
-    case KERN_256x256:
-      return h16 ? launch_bf16<256, 256, 2, 4, 0, true>(a, s) : launch_bf16<256, 256, 2, 4, 0, false>(a, s);
-    case KERN_320x256:
-      return h16 ? launch_bf16<320, 256, 2, 4, 0, true>(a, s) : launch_bf16<320, 256, 2, 4, 0, false>(a, s);
-    case KERN_128x128:
-      return h16 ? launch_bf16<128, 128, 2, 2, 0, true>(a, s) : launch_bf16<128, 128, 2, 2, 0, false>(a, s);
-    case KERN_64x64:
-      return h16 ? launch_bf16<64, 64, 2, 2, 0, true>(a, s) : launch_bf16<64, 64, 2, 2, 0, false>(a, s);
-    case KERN_256x128:
-      return h16 ? launch_bf16<256, 128, 4, 2, 0, true>(a, s) : launch_bf16<256, 128, 4, 2, 0, false>(a, s);
-    default:
-      if (!fits) return h16 ? launch_bf16<320, 256, 2, 4, 0, true>(a, s) : launch_bf16<320, 256, 2, 4, 0, false>(a, s);
-      return h16 ? launch_bf16_8ph<true, true>(a, s) : launch_bf16_8ph<false, true>(a, s);
-  }
+  if (in_dtype == AACLIP_F16) return dispatch16<true, true>(a, (hipStream_t)stream);
+  return dispatch16<false, true>(a, (hipStream_t)stream);
 }
 
 extern "C" int aaclip_gemm_fp8(int out_dtype, int M, int N, int K, const void* A, int64_t lda,
@@ -1536,16 +1430,13 @@ extern "C" int aaclip_gemm_fp8(int out_dtype, int M, int N, int K, const void* A
   AACLIP_REQUIRE(lda >= K && ldw >= K && ldc >= N && lda % 16 == 0 && ldw % 16 == 0 && ldc % 4 == 0);
   AACLIP_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)C % 16) == 0);
   AACLIP_REQUIRE(((uintptr_t)w_scale % 16) == 0);
-  AACLIP_REQUIRE(!(epilogue & AACLIP_EPI_BIAS) || (bias && ((uintptr_t)bias % 16) == 0));
-  AACLIP_REQUIRE(!(epilogue & AACLIP_EPI_RESID) || (residual && ldr >= N && ldr % 4 == 0));
-  AACLIP_REQUIRE(!(epilogue & AACLIP_EPI_AUX_BF16) || (aux && ldaux >= N && ldaux % 4 == 0));
-  AACLIP_REQUIRE((epilogue & ~63) == 0 && (epilogue & (AACLIP_EPI_GELU | AACLIP_EPI_QGELU)) !=
-                                               (AACLIP_EPI_GELU | AACLIP_EPI_QGELU));
+  AACLIP_REQUIRE(check_epilogue_args(epilogue, bias, residual, ldr, aux, ldaux, N, 4));
   AACLIP_REQUIRE(row_group >= 0 && (row_group == 0 || row_group_out >= row_group));
   if (M == 0) return AACLIP_OK;
-  GemmArgs a{A, W, C, bias, residual, aux, lda, ldw, ldc, ldr, ldaux, M, N, K, epilogue,
-             out_dtype, row_group, row_group_out, row_offset, 0, 0, g_group_m, g_setprio, 0,
-             a_scale, w_scale, nullptr, 0, nullptr, 0};
+  GemmArgs a = gemm_args(A, lda, W, ldw, C, ldc, M, N, K, epilogue, out_dtype);
+  a.bias = bias, a.res = residual, a.ldr = ldr, a.aux = aux, a.ldaux = ldaux;
+  a.row_group = row_group, a.row_group_out = row_group_out, a.row_offset = row_offset;
+  a.a_scale = a_scale, a.w_scale = w_scale;
   hipStream_t s = (hipStream_t)stream;
   if (N % 256 == 0) return launch_bf16<256, 256, 2, 4, 1>(a, s);  // 320x256 spills with 8-VGPR fp8 fragments
   return launch_bf16<256, 128, 4, 2, 1>(a, s);
@@ -1566,21 +1457,18 @@ extern "C" int aaclip_gemm_fp8mx(int out_dtype, int M, int N, int K, const void*
   AACLIP_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)C % 16) == 0);
   AACLIP_REQUIRE(((uintptr_t)w_scale % 16) == 0 && ((uintptr_t)a_mx % 4) == 0);
   AACLIP_REQUIRE((int64_t)(K / 128) * ld_amx * 2 < (1ll << 31) && (int64_t)M * lda < (1ll << 31));
-  AACLIP_REQUIRE(!(epilogue & AACLIP_EPI_BIAS) || (bias && ((uintptr_t)bias % 16) == 0));
-  AACLIP_REQUIRE(!(epilogue & AACLIP_EPI_RESID) || (residual && ldr >= N && ldr % 4 == 0));
-  AACLIP_REQUIRE(!(epilogue & AACLIP_EPI_AUX_BF16) || (aux && ldaux >= N && ldaux % 4 == 0));
-  AACLIP_REQUIRE((epilogue & ~63) == 0 && (epilogue & (AACLIP_EPI_GELU | AACLIP_EPI_QGELU)) !=
-                                               (AACLIP_EPI_GELU | AACLIP_EPI_QGELU));
+  AACLIP_REQUIRE(check_epilogue_args(epilogue, bias, residual, ldr, aux, ldaux, N, 4));
   AACLIP_REQUIRE(out_dtype != AACLIP_FP8 || (c_mx && ld_cmx >= M && (epilogue == (AACLIP_EPI_BIAS | AACLIP_EPI_GELU) ||
                                                          epilogue == (AACLIP_EPI_BIAS | AACLIP_EPI_QGELU))));
   if (M == 0) return AACLIP_OK;
-  GemmArgs a{A, W, C, bias, residual, aux, lda, ldw, ldc, ldr, ldaux, M, N, K, epilogue,
-             out_dtype, 0, 0, 0, 0, 0, g_group_m, g_setprio, g_dbg,
-             nullptr, w_scale, (const uint8_t*)a_mx, ld_amx, (uint8_t*)c_mx, ld_cmx};
+  GemmArgs a = gemm_args(A, lda, W, ldw, C, ldc, M, N, K, epilogue, out_dtype);
+  a.bias = bias, a.res = residual, a.ldr = ldr, a.aux = aux, a.ldaux = ldaux;
+  a.dbg = g_dbg;
+  a.w_scale = w_scale, a.a_mx = (const uint8_t*)a_mx, a.ld_amx = ld_amx, a.c_mx = (uint8_t*)c_mx, a.ld_cmx = ld_cmx;
   // 8-phase ping-pong by default (C5 at B=32: qkv/fc/out +6-8%, c_proj +28% vs the
   // 256x256 LDS-DMA kernel; whole C5 step 1400 -> 1511 img/s); variant 6 = A/B hook
   if (g_gemm_variant == 6) return launch_bf16<256, 256, 2, 4, 2>(a, (hipStream_t)stream);
-  return launch_fp8mx_8ph(a, (hipStream_t)stream);
+  return launch_8ph<2, false, false>(a, (hipStream_t)stream);
 }
 
 AACLIP_TRACE_SETTER(trace_set_gemm)

@@ -276,6 +276,94 @@ def test_gemm_fp8mx_8ph_race_screen(dev, K):
         _lib.call("aaclip_set_gemm_variant", 0)
 
 
+# (bias, activation, residual, aux, C dtype) -- five with a compile-time case in the 8-phase MX kernel,
+# then three that take its run-time-flag fallback
+MX_EDGE_EPILOGUES = ((True, None, False, False, torch.bfloat16), (True, None, True, False, torch.float32),
+                     (True, None, True, True, torch.float32), (True, "gelu", False, False, FP8),
+                     (True, "quick", False, False, FP8),
+                     (False, None, False, False, torch.float32), (False, "leaky", False, False, torch.float32),
+                     (True, None, True, False, torch.bfloat16))
+MX_SENTINEL = 0x5A
+
+
+def test_gemm_fp8mx_epilogues_at_tile_edges(dev):
+    """The 8-phase MX kernel's LDS epilogue at the edges of its 256x256 tile: M = 1, 255, 257 (one row,
+    one short of a tile, one row into the second), N = 256 and 512 (one and two tile columns), K = 128,
+    256, 384 (1, 2, 3 K-steps: the prologue-only path, the counted tail alone, one steady-state pass),
+    with the eight epilogues rotating over the 18 shapes. (a) C, the aux copy and the output scales equal
+    those of the 256x256 LDS-DMA kernel (variant 6) bit for bit; (b) fp32 outputs are within this file's
+    bound 6e-5 * (|A| @ |W|^T) + 1e-6 of float64 on the dequantised operands, the residual added in
+    float64 -- a bf16 C within that plus its own rounding, 2^-8 |ref| (8 significant bits: half an ulp
+    is at most 2^-8 |x|), and the aux copy is C rounded once; (c) fp8 outputs within the bound of
+    test_gemm_fp8mx_gelu_fp8_output_chain, and rows >= M of the padded output and of its scales keep
+    their sentinel."""
+    seen = set()
+    i = 0
+    try:
+        for M in (1, 255, 257):
+            for N in (256, 512):
+                for K in (128, 256, 384):
+                    has_bias, act, has_res, has_aux, cdt = MX_EDGE_EPILOGUES[i % len(MX_EDGE_EPILOGUES)]
+                    seen.add(i % len(MX_EDGE_EPILOGUES))
+                    i += 1
+                    what = f"M {M} N {N} K {K} bias {has_bias} act {act} resid {has_res} aux {has_aux} -> {cdt}"
+                    torch.manual_seed(M + N * 3 + K)
+                    a = torch.randn(M, K, device=dev) * torch.logspace(-2, 2, K // 64, device=dev).repeat_interleave(64)
+                    w = torch.randn(N, K, device=dev) * K ** -0.5
+                    a8 = torch.empty(M, K, device=dev, dtype=FP8)
+                    ld = (M + 7) // 2 * 2  # padded, even
+                    asc = ops.mx_scales(M, K, dev, ld=ld)
+                    ops.quant_fp8_mx(a, a8, asc)
+                    w8, sw = _wq(w)
+                    bias = torch.randn(N, device=dev) * 0.1 if has_bias else None
+                    res = torch.randn(M, N, device=dev) if has_res else None
+                    rows = M + 3 if cdt == FP8 else M
+
+                    def run(variant):
+                        _lib.call("aaclip_set_gemm_variant", variant)
+                        if cdt == FP8:
+                            c = torch.full((rows, N), MX_SENTINEL, device=dev, dtype=torch.uint8).view(FP8)
+                            csc = torch.full((N // 128, ld, 2), MX_SENTINEL, device=dev, dtype=torch.uint8)
+                        else:
+                            c, csc = torch.full((rows, N), -7.25, device=dev, dtype=cdt), None
+                        aux = torch.full((M, N), -7.25, device=dev, dtype=torch.bfloat16) if has_aux else None
+                        ops.gemm_fp8mx(a8, asc, w8, sw, c, out_sc=csc, bias=bias, gelu={"gelu": True, "quick": "quick"}.get(act, False),
+                                       leaky=act == "leaky", residual=res, aux=aux)
+                        return c, aux, csc
+
+                    c, aux, csc = run(0)
+                    c6, aux6, csc6 = run(6)
+                    # (a) the two kernels: the same fp32 sums in the same K order through the same epilogue arithmetic
+                    assert torch.equal(c.view(torch.uint8), c6.view(torch.uint8)), f"{what}: C differs from variant 6"
+                    assert aux is None or torch.equal(aux, aux6), f"{what}: aux differs from variant 6"
+                    assert csc is None or torch.equal(csc, csc6), f"{what}: out_sc differs from variant 6"
+                    A = _mx_dequant(a8, asc)
+                    Wd = w8.double() * sw.double()[:, None]
+                    pre = A @ Wd.T + (bias.double() if has_bias else 0.0)
+                    tol = 6e-5 * (A.abs() @ Wd.abs().T) + 1e-6
+                    if cdt == FP8:  # (c)
+                        g_ref = pre * torch.sigmoid(1.702 * pre) if act == "quick" else torch.nn.functional.gelu(pre)
+                        g = _mx_dequant(c[:M], csc)
+                        blk = g_ref.abs().view(M, N // 64, 64).amax(-1).repeat_interleave(64, dim=1)
+                        err, bound = (g - g_ref).abs(), 2.0 ** -4 * g_ref.abs() + blk * 2.0 ** -8 + 1e-4
+                        print(f"{what}: worst fp8 error / bound {(err / bound).max().item():.3f}")
+                        assert (err <= bound).all(), what
+                        assert (c.view(torch.uint8)[M:] == MX_SENTINEL).all(), f"{what}: wrote C rows >= M"
+                        assert (csc[:, M:] == MX_SENTINEL).all(), f"{what}: wrote the scales of rows >= M"
+                    else:  # (b)
+                        ref = torch.nn.functional.leaky_relu(pre, 0.01) if act == "leaky" else pre
+                        if has_res:
+                            ref = ref + res.double()
+                        bound = tol + (2.0 ** -8 * ref.abs() if cdt == torch.bfloat16 else 0.0)
+                        err = (c.double() - ref).abs()
+                        print(f"{what}: worst error / bound {(err / bound).max().item():.3f}")
+                        assert (err <= bound).all(), what
+                        assert aux is None or torch.equal(aux, c.to(torch.bfloat16)), f"{what}: aux is not C rounded once"
+    finally:
+        _lib.call("aaclip_set_gemm_variant", 0)
+    assert seen == set(range(len(MX_EDGE_EPILOGUES)))
+
+
 def test_layernorm_kernels_mx_output(dev):
     """LayerNorm / block-tail / embed rows written straight to MX fp8 equal the MX
     quantisation of the same kernels' fp32 rows, bit for bit (same fp32 values, same

@@ -10,9 +10,9 @@ B=/tmp/aaclip_ab_build/$NAME
 mkdir -p "$B" "$R/ab"
 cd "$R/aa-clip_amd/csrc"
 FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall -Wno-unused-function -I../../include"
-for f in gemm attention rows anomaly_map metrics preprocess version; do
+for f in $(sed -n 's/^SRCS := //p' Makefile | sed 's/\.hip//g'); do  # the Makefile's list and per-file flags
   extra=""
-  [ $f = attention ] && extra=-fno-honor-nans
+  { [ $f = attention ] || [ $f = bank ]; } && extra=-fno-honor-nans
   /opt/rocm/bin/hipcc $FLAGS $extra "$@" -c $f.hip -o "$B/$f.o" &
 done
 wait

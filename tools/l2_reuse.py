@@ -59,7 +59,8 @@ def summarize(root, out=None):
     for f in sorted(glob.glob(os.path.join(root, "pmc*", "*counter_collection.csv"))):
         rows = collections.defaultdict(dict)
         for r in csv.DictReader(open(f)):
-            if "gemm_bf16_8ph" not in r["Kernel_Name"]:
+            # the 16-bit 8-phase kernel: gemm_8ph_kernel<0, ...>, gemm_bf16_8ph_kernel<...> in older CSVs
+            if "gemm_8ph_kernel<0" not in r["Kernel_Name"] and "gemm_bf16_8ph" not in r["Kernel_Name"]:
                 continue
             rows[int(r["Dispatch_Id"])][r["Counter_Name"]] = float(r["Counter_Value"])
         per_pass.append([rows[k] for k in sorted(rows)])

@@ -50,7 +50,9 @@ if __name__ == "__main__":
         # C2 (B=32, M = 18464): QKV and c_fc launches of 512-thread workgroups, on the
         # 320x256 kernel (58 x 12 / 58 x 16 tiles) or the 8-phase 256x256 one (73 x 12 / 73 x 16)
         grids = {696 * 512, 928 * 512, 876 * 512, 1168 * 512}
-        gemm = [e for e in s if "gemm_bf16" in e["kernel"] and e["grid_size"] in grids and "hbm_bytes" in e]
+        # (gemm_8ph_kernel<0, ...>; gemm_bf16_8ph_kernel<...> in older CSVs matches "gemm_bf16" too)
+        gemm = [e for e in s if ("gemm_bf16" in e["kernel"] or "gemm_8ph_kernel<0" in e["kernel"]) and
+                e["grid_size"] in grids and "hbm_bytes" in e]
         # the map as predict() runs it since round 4: partial_scores + blur_upsample_score
         # (the row form, patch_scores + blur_upsample, when a summary holds only that)
         mp = [e for e in s if "partial_scores" in e["kernel"] and "hbm_bytes" in e]
