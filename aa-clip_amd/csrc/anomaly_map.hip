@@ -13,6 +13,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "rowmath.h"  // the wave-row layout: load_row_as, load_anchors
 
 namespace {
 
@@ -20,17 +21,6 @@ constexpr int kMaxLevels = 8;
 struct LevelPtrs {
   const void* p[kMaxLevels];
 };
-
-// The lane's 12 anchor channels (C = 768 = 3 x 256): t0 / t1 = normal / abnormal.
-__device__ __forceinline__ void load_anchors(const float* T, float4_t (&t0)[3], float4_t (&t1)[3], int lane) {
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float* tp = T + 2 * (256 * c + 4 * lane);
-    float4_t a = *(const float4_t*)tp, b = *(const float4_t*)(tp + 4);
-    t0[c] = float4_t{a[0], a[2], b[0], b[2]};
-    t1[c] = float4_t{a[1], a[3], b[1], b[3]};
-  }
-}
 
 // One patch row through every level (one wave): loads of all levels issued before
 // the reductions (memory-level parallelism), then ||f||, f.t0, f.t1 per level.
@@ -50,19 +40,7 @@ __device__ __forceinline__ float patch_row_score(LevelPtrs lv, int nl, int64_t l
 #pragma unroll
   for (int l = 0; l < NLMAX; ++l) {
     if (l < nl) {
-      if constexpr (F32IN) {
-        const float* p = (const float*)lv.p[l] + row * ld;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) f[l][c] = *(const float4_t*)(p + 256 * c + 4 * lane);
-      } else {
-        const uint16_t* p = (const uint16_t*)lv.p[l] + row * ld;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          uint2 r = *(const uint2*)(p + 256 * c + 4 * lane);
-          f[l][c] = float4_t{__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u),
-                             __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u)};
-        }
-      }
+      load_row_as<F32IN, 3>(lv.p[l], row * ld, f[l], lane);
     }
   }
   float acc = 0.f;
@@ -129,19 +107,10 @@ __global__ __launch_bounds__(256) void patch_logits_kernel(int in_dtype, const v
   if (row >= rows) return;
   T += (size_t)(row / group) * t_stride;
   float4_t v[3];
-  if (in_dtype == AACLIP_F32) {
-    const float* p = (const float*)f + (size_t)row * ld;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = *(const float4_t*)(p + 256 * c + 4 * lane);
-  } else {
-    const uint16_t* p = (const uint16_t*)f + (size_t)row * ld;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      uint2 r = *(const uint2*)(p + 256 * c + 4 * lane);
-      v[c] = float4_t{__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u),
-                      __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u)};
-    }
-  }
+  if (in_dtype == AACLIP_F32)
+    load_row_as<true, 3>(f, (size_t)row * ld, v, lane);
+  else
+    load_row_as<false, 3>(f, (size_t)row * ld, v, lane);
   const size_t base = (size_t)(row / group) * n_anchor * group + row % group;
   for (int a = 0; a < n_anchor; ++a) {
     float d = 0.f;
@@ -431,19 +400,10 @@ __global__ __launch_bounds__(64 * kDetRows) void map_det_kernel(int64_t ld, cons
     float4_t v[3] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
     if (p < n_patch) {
       const size_t row = (size_t)b * n_patch + p;
-      if constexpr (F32IN) {
-        const float* q = (const float*)det + row * ld;
+      float4_t f[3];  // loaded beside v: loading into v itself renumbers the registers of its zero fill
+      load_row_as<F32IN, 3>(det, row * ld, f, lane);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = *(const float4_t*)(q + 256 * c + 4 * lane);
-      } else {
-        const uint16_t* q = (const uint16_t*)det + row * ld;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          uint2 r = *(const uint2*)(q + 256 * c + 4 * lane);
-          v[c] = float4_t{__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u),
-                          __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u)};
-        }
-      }
+      for (int c = 0; c < 3; ++c) v[c] = f[c];
       float ss = 0.f;
 #pragma unroll
       for (int c = 0; c < 3; ++c)
@@ -577,39 +537,50 @@ extern "C" int aaclip_patch_logits_per_image(int in_dtype, const void* f, int64_
   return AACLIP_OK;
 }
 
-// LDS bytes stage 2 needs for C channels: the source rows a band's taps can reach.
-static size_t blur_upsample_lds(int C, int g, int S, int ksize) {
-  const float scale = (float)(g - 1) / (float)(S - 1);
-  const int span = (int)(scale * (float)(kBand - 1)) + 4;  // source rows a band's taps can reach (+1 margin)
-  const int brows = min(g, span);
-  const int xrows = min(g, brows + 2 * (ksize / 2));
-  return (size_t)C * (2 * xrows + brows) * g * sizeof(float);
+// What stage 2 needs for (C channels, grid g, output S, ksize): the bilinear scale, the source
+// rows a band's taps can reach (brows), those plus their blur neighbourhood (xrows), and the
+// LDS bytes that holds them.
+struct BlurPlan {
+  float scale;
+  int brows, xrows;
+  size_t lds;
+};
+static BlurPlan blur_plan(int C, int g, int S, int ksize) {
+  BlurPlan p;
+  p.scale = (float)(g - 1) / (float)(S - 1);
+  const int span = (int)(p.scale * (float)(kBand - 1)) + 4;  // source rows a band's taps can reach (+1 margin)
+  p.brows = min(g, span);
+  p.xrows = min(g, p.brows + 2 * (ksize / 2));
+  p.lds = (size_t)C * (2 * p.xrows + p.brows) * g * sizeof(float);
+  return p;
 }
 
 // Every argument check of aaclip_blur_upsample, so the multi-launch entry points can
 // reject a bad call before their first launch (no half-written map on an error).
 static bool blur_upsample_args_ok(int channels, int g, int out_size, int ksize) {
   return channels >= 1 && channels <= kMaxC && g >= 2 && g <= 64 && out_size >= 2 && ksize >= 0 && ksize <= 15 &&
-         (ksize == 0 || (ksize % 2 == 1 && ksize / 2 < g)) && blur_upsample_lds(channels, g, out_size, ksize) <= 64 * 1024;
+         (ksize == 0 || (ksize % 2 == 1 && ksize / 2 < g)) && blur_plan(channels, g, out_size, ksize).lds <= 64 * 1024;
 }
+
+// ksize at compile time for the domains' 7 and 9 and for no blur, else at run time (K = -1):
+// the macro binds K, the launch expression passed to it names it
+#define DISPATCH_KSIZE(ksize, ...)                         \
+  switch ((ksize)) {                                       \
+    case 0: { constexpr int K = 0; __VA_ARGS__; break; }   \
+    case 7: { constexpr int K = 7; __VA_ARGS__; break; }   \
+    case 9: { constexpr int K = 9; __VA_ARGS__; break; }   \
+    default: { constexpr int K = -1; __VA_ARGS__; break; } \
+  }
 
 // Launch stage 2 for (C, ksize): rows of LDS the band needs, sized on the host.
 template <int C>
 int launch_blur_upsample(const float* grid, float* out, int batch, int g, int S, int ksize, const Gauss& gw,
-                         int softmax, float scale, hipStream_t s) {
-  const int span = (int)(scale * (float)(kBand - 1)) + 4;  // source rows a band's taps can reach (+1 margin)
-  const int brows = min(g, span);
-  const int xrows = min(g, brows + 2 * (ksize / 2));
-  const size_t lds = blur_upsample_lds(C, g, S, ksize);
-  if (lds > 64 * 1024) return AACLIP_ERR_ARG;
+                         int softmax, hipStream_t s) {
+  const BlurPlan p = blur_plan(C, g, S, ksize);
+  if (p.lds > 64 * 1024) return AACLIP_ERR_ARG;
   const dim3 grd(ceil_div(S, kBand), batch);
-#define BU_LAUNCH(K) \
-  blur_upsample_kernel<C, K><<<grd, 64, lds, s>>>(grid, out, g, S, ksize, gw, softmax, scale, xrows, brows)
-  if (ksize == 0) BU_LAUNCH(0);
-  else if (ksize == 7) BU_LAUNCH(7);
-  else if (ksize == 9) BU_LAUNCH(9);
-  else BU_LAUNCH(-1);
-#undef BU_LAUNCH
+  DISPATCH_KSIZE(ksize, blur_upsample_kernel<C, K><<<grd, 64, p.lds, s>>>(grid, out, g, S, ksize, gw, softmax,
+                                                                        p.scale, p.xrows, p.brows));
   return AACLIP_OK;
 }
 
@@ -619,18 +590,17 @@ extern "C" int aaclip_blur_upsample(const float* grid, float* out, int batch, in
   AACLIP_REQUIRE(grid && out && batch > 0);
   AACLIP_REQUIRE(blur_upsample_args_ok(channels, g, out_size, ksize));
   const Gauss gw = ksize > 0 ? gaussian_weights(ksize, sigma) : Gauss{};
-  const float scale = (float)(g - 1) / (float)(out_size - 1);
   hipStream_t s = (hipStream_t)stream;
   int rc = AACLIP_ERR_ARG;
   switch (channels) {
-    case 1: rc = launch_blur_upsample<1>(grid, out, batch, g, out_size, ksize, gw, softmax, scale, s); break;
-    case 2: rc = launch_blur_upsample<2>(grid, out, batch, g, out_size, ksize, gw, softmax, scale, s); break;
-    case 3: rc = launch_blur_upsample<3>(grid, out, batch, g, out_size, ksize, gw, softmax, scale, s); break;
-    case 4: rc = launch_blur_upsample<4>(grid, out, batch, g, out_size, ksize, gw, softmax, scale, s); break;
-    case 5: rc = launch_blur_upsample<5>(grid, out, batch, g, out_size, ksize, gw, softmax, scale, s); break;
-    case 6: rc = launch_blur_upsample<6>(grid, out, batch, g, out_size, ksize, gw, softmax, scale, s); break;
-    case 7: rc = launch_blur_upsample<7>(grid, out, batch, g, out_size, ksize, gw, softmax, scale, s); break;
-    default: rc = launch_blur_upsample<8>(grid, out, batch, g, out_size, ksize, gw, softmax, scale, s); break;
+    case 1: rc = launch_blur_upsample<1>(grid, out, batch, g, out_size, ksize, gw, softmax, s); break;
+    case 2: rc = launch_blur_upsample<2>(grid, out, batch, g, out_size, ksize, gw, softmax, s); break;
+    case 3: rc = launch_blur_upsample<3>(grid, out, batch, g, out_size, ksize, gw, softmax, s); break;
+    case 4: rc = launch_blur_upsample<4>(grid, out, batch, g, out_size, ksize, gw, softmax, s); break;
+    case 5: rc = launch_blur_upsample<5>(grid, out, batch, g, out_size, ksize, gw, softmax, s); break;
+    case 6: rc = launch_blur_upsample<6>(grid, out, batch, g, out_size, ksize, gw, softmax, s); break;
+    case 7: rc = launch_blur_upsample<7>(grid, out, batch, g, out_size, ksize, gw, softmax, s); break;
+    default: rc = launch_blur_upsample<8>(grid, out, batch, g, out_size, ksize, gw, softmax, s); break;
   }
   if (rc) return rc;
   AACLIP_CHECK_LAUNCH();
@@ -667,24 +637,15 @@ extern "C" int aaclip_anomaly_map_partials(const float* part, int64_t ld_part, i
                                                                          grid_ws, det_ws);
   AACLIP_CHECK_LAUNCH();
   const Gauss gw = ksize > 0 ? gaussian_weights(ksize, sigma) : Gauss{};
-  const float scale = (float)(g - 1) / (float)(out_size - 1);
-  const int span = (int)(scale * (float)(kBand - 1)) + 4;  // as launch_blur_upsample
-  const int brows = min(g, span);
-  const int xrows = min(g, brows + 2 * (ksize / 2));
-  const size_t lds = blur_upsample_lds(1, g, out_size, ksize);
+  const BlurPlan p = blur_plan(1, g, out_size, ksize);
   const dim3 grd(ceil_div(out_size, kBand), batch);
   const float* dr = with_det ? det_ws : nullptr;
-#define BS_LAUNCH(K)                                                                                      \
-  blur_upsample_score_kernel<K><<<grd, 64, lds, s>>>(grid_ws, out, g, out_size, ksize, gw, scale, xrows, brows, \
-                                                     dr, g * g, score)
-  if (ksize == 0) BS_LAUNCH(0);
-  else if (ksize == 7) BS_LAUNCH(7);
-  else if (ksize == 9) BS_LAUNCH(9);
-  else BS_LAUNCH(-1);
-#undef BS_LAUNCH
+  DISPATCH_KSIZE(ksize, blur_upsample_score_kernel<K><<<grd, 64, p.lds, s>>>(
+                            grid_ws, out, g, out_size, ksize, gw, p.scale, p.xrows, p.brows, dr, g * g, score));
   AACLIP_CHECK_LAUNCH();
   return AACLIP_OK;
 }
+#undef DISPATCH_KSIZE
 
 extern "C" int aaclip_image_score(int in_dtype, const void* det_raw, int64_t ld, const float* T,
                                   int batch, int n_patch, int channels, int normalize,

@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "attn_lds.h"  // tr_read, swz, kAttnLog2Scale
+#include "mxfp8.h"
 
 namespace {
 
@@ -499,9 +500,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? ATTN_OCC : 4) void attn_bf16_ker
 
   // ---- epilogue: O[q][d = db*16 + 4g + i] = ot / l
   if (!H16 && out_mx) {
-    // MX fp8 output (config C5, the out-proj input): one head = one 64-column block,
-    // held by the 4 lanes {c, c+16, c+32, c+48}: block max over them, e8m0 scale,
-    // RNE e4m3, 4x4 dword transpose so lane g owns columns 16g..16g+15 -> 16-B stores
+    // MX fp8 output (config C5, the out-proj input; the format and every step are mxfp8.h's):
+    // one head = one 64-column block, held by the 4 lanes {c, c+16, c+32, c+48}. mx_quant_row's
+    // steps written out, with 1 / l folded into the one scale factor and the file's own
+    // max_over_groups: called as a function they renumber this kernel's registers. On exit lane g
+    // owns columns 16g..16g+15 -> 16-B stores
     uint8_t* o8 = (uint8_t*)out;
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {
@@ -512,38 +515,16 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? ATTN_OCC : 4) void attn_bf16_ker
       for (int db = 0; db < 4; ++db)
 #pragma unroll
         for (int i = 0; i < 4; ++i) amax = fmaxf(amax, fabsf(ot[qb][db][i] * inv));
-      amax = max_over_groups(amax);
-      int e = 0;
-      if (amax > 0.f) {
-        int x;
-        (void)frexpf(amax, &x);
-        e = x - 9;
-        if (ldexpf(amax, -e) > 448.f) e += 1;
-        e = max(min(e, 127), -126);
-      }
-      const float s = inv * __uint_as_float((uint32_t)(127 - e) << 23);
+      const int e = mx_exp(max_over_groups(amax));
+      const float s = inv * pow2i(-e);
       uint32_t d[4];
 #pragma unroll
-      for (int db = 0; db < 4; ++db) {
-        uint32_t w = __builtin_amdgcn_cvt_pk_fp8_f32(ot[qb][db][0] * s, ot[qb][db][1] * s, 0, false);
-        d[db] = __builtin_amdgcn_cvt_pk_fp8_f32(ot[qb][db][2] * s, ot[qb][db][3] * s, w, true);
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        auto r = __builtin_amdgcn_permlane32_swap(d[j], d[j + 2], false, false);
-        d[j] = r[0];
-        d[j + 2] = r[1];
-      }
-#pragma unroll
-      for (int k = 0; k < 4; k += 2) {
-        auto r = __builtin_amdgcn_permlane16_swap(d[k], d[k + 1], false, false);
-        d[k] = r[0];
-        d[k + 1] = r[1];
-      }
+      for (int db = 0; db < 4; ++db) d[db] = mx_pack4(ot[qb][db][0], ot[qb][db][1], ot[qb][db][2], ot[qb][db][3], s);
+      transpose_fq(d);
       if (q < N) {
         const size_t row = (size_t)b * N + q;
         *(uint4*)(o8 + row * HDt + h * HD_ + 16 * g) = uint4{d[0], d[1], d[2], d[3]};
-        if (g == 0) out_mx[((size_t)(h >> 1) * ld_mx + row) * 2 + (h & 1)] = (uint8_t)(e + 127);
+        if (g == 0) *mx_scale_ptr(out_mx, ld_mx, row, h) = (uint8_t)(e + 127);
       }
     }
     return;

@@ -127,6 +127,26 @@ __device__ __forceinline__ float gelu_erf(float v) {
 __device__ __forceinline__ float qgelu_exact(float v) { return v * (1.0f / (1.0f + expf(-1.702f * v))); }
 // nn.LeakyReLU(0.01), written as the epilogue writes it
 __device__ __forceinline__ float leaky_relu(float v) { return v >= 0.f ? v : 0.01f * v; }
+// The derivative of the activation `mode` (its GEMM epilogue flag, AACLIP_EPI_GELU / _QGELU /
+// _LEAKY) at the reference value v, for aaclip_act_bwd and aaclip_act_bwd16. GELU / QuickGELU:
+// v = the pre-activation; gelu'(v) = Phi(v) + v phi(v), quick'(v) = s + 1.702 v s (1 - s),
+// s = sigmoid(1.702 v). LeakyReLU: v = the OUTPUT (its sign is the input's); slope 1 above 0,
+// 0.01 at and below 0 (torch's leaky_relu_backward).
+__device__ __forceinline__ float act_slope(int mode, float v) {
+  if (mode == AACLIP_EPI_GELU) {
+    const float cdf = 0.5f * (1.0f + erff(v * 0.70710678118654752440f));
+    return cdf + v * (0.39894228040143267794f * expf(-0.5f * v * v));
+  }
+  if (mode == AACLIP_EPI_QGELU) {
+    const float s = 1.0f / (1.0f + expf(-1.702f * v));
+    return s + 1.702f * v * s * (1.0f - s);
+  }
+  return v > 0.f ? 1.0f : 0.01f;
+}
+// host side: the modes the elementwise activation entry points accept
+inline bool act_mode_ok(int mode) {
+  return mode == AACLIP_EPI_GELU || mode == AACLIP_EPI_QGELU || mode == AACLIP_EPI_LEAKY;
+}
 
 // ---------------------------------------------------------------- 16-bit activations
 // The forms the 16-bit GEMM epilogues apply (gemm.hip wave_epilogue / wave_epilogue_lds). Shared

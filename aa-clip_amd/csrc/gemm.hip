@@ -24,7 +24,7 @@
 //     output row remap (patch rows -> token rows after the CLS slot), MX fp8 output, score
 //     partials. wave_epilogue stores straight from the accumulators, wave_epilogue_lds
 //     (8-phase) quad-coalesced through LDS; the bias / scale loads, the activation chain,
-//     the MX quantisation and the c_mx address are one copy both call (epi_*, mx_quant_row).
+//     the MX quantisation and the c_mx address are one copy both call (epi_*; mxfp8.h mx_quant_row).
 // fp32 kernel (parity mode): v_mfma_f32_16x16x4_f32 (exact fp32 FMA chain),
 //   64x64x16 register-staged tiles. Same epilogue, one element at a time.
 #include <math.h>
@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mxfp8.h"
 
 namespace {
 
@@ -72,25 +73,6 @@ __host__ __device__ inline uint32_t gemm_trace_tag(const GemmArgs& a) {
   return (uint32_t)min(a.N / 64, 255) << 4 | (uint32_t)min(a.K / 64, 255) << 12 | (uint32_t)a.epi << 20;
 }
 
-// smallest e with amax * 2^-e <= 448 (largest finite e4m3): the e8m0 block scale
-__device__ __forceinline__ int mx_exp(float amax) {
-  if (!(amax > 0.f)) return 0;
-  int x;
-  (void)frexpf(amax, &x);  // amax = m * 2^x, m in [0.5, 1)
-  int e = x - 9;           // amax * 2^-e in [256, 512)
-  if (ldexpf(amax, -e) > 448.f) e += 1;
-  return max(min(e, 127), -126);
-}
-__device__ __forceinline__ float pow2i(int e) { return __uint_as_float((uint32_t)(e + 127) << 23); }
-
-// cross-lane max over the 4 lanes {c, c+16, c+32, c+48} (one row of the C^T tile)
-__device__ __forceinline__ float max_over_fq(float v) {
-  auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-  auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-
 // sum over the 4 lanes {c, c+16, c+32, c+48} in a fixed association, (fq0 + fq1) + (fq2 + fq3)
 // with the pairs' operands swapped on the partner lanes -- fp32 addition commutes, so all
 // four lanes end with the same bits
@@ -99,24 +81,6 @@ __device__ __forceinline__ float sum_over_fq(float v) {
   v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
   auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
   return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
-// 4x4 dword transpose across the lane groups fq = lane/16: on entry lane fq holds
-// d[j] = its 4 fp8 columns of column tile j; on exit it holds tile j = fq's 16
-// consecutive bytes (d[q] = the 4 columns of lane group q).
-__device__ __forceinline__ void transpose_fq(uint32_t (&d)[4]) {
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    auto r = __builtin_amdgcn_permlane32_swap(d[j], d[j + 2], false, false);
-    d[j] = r[0];
-    d[j + 2] = r[1];
-  }
-#pragma unroll
-  for (int k = 0; k < 4; k += 2) {
-    auto r = __builtin_amdgcn_permlane16_swap(d[k], d[k + 1], false, false);
-    d[k] = r[0];
-    d[k + 1] = r[1];
-  }
 }
 
 __device__ __forceinline__ int remap_row(const GemmArgs& a, int m) {
@@ -201,30 +165,9 @@ __device__ __forceinline__ void epi_load_cols(const GemmArgs& a, int epi, const 
   }
 }
 
-// MX quantisation of one row's 64-column block (lane (fr, fq) holds columns 16 j + 4 fq .. + 3
-// of tile j): row max over the 4 lane groups, power-of-two scale, RNE to e4m3, 4x4 lane-group
-// transpose. On exit d = the row's bytes 16 fq .. 16 fq + 15; returns the block exponent.
-__device__ __forceinline__ int mx_quant_row(const float4_t (&v)[4], uint32_t (&d)[4]) {
-  float amax = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int t = 0; t < 4; ++t) amax = fmaxf(amax, fabsf(v[j][t]));
-  const int e = mx_exp(max_over_fq(amax));
-  const float inv = pow2i(-e);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    uint32_t w = __builtin_amdgcn_cvt_pk_fp8_f32(v[j][0] * inv, v[j][1] * inv, 0, false);
-    d[j] = __builtin_amdgcn_cvt_pk_fp8_f32(v[j][2] * inv, v[j][3] * inv, w, true);
-  }
-  transpose_fq(d);
-  return e;
-}
-
 // the e8m0 byte of output row orow for the 64-column block that starts at column nw
 __device__ __forceinline__ uint8_t* c_mx_addr(const GemmArgs& a, int nw, size_t orow) {
-  const int blk = nw >> 6;
-  return a.c_mx + ((size_t)(blk >> 1) * a.ld_cmx + orow) * 2 + (blk & 1);
+  return mx_scale_ptr(a.c_mx, a.ld_cmx, orow, nw >> 6);
 }
 
 // the activation under EPI, on a lane's 4 columns of one column tile

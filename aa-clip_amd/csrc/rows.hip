@@ -2,59 +2,15 @@
 // post-block tail (adapter blend + next ln_1 + level tap/ln_post), text
 // embedding, EOT gather, anchor reduction, L2 normalisation, im2col.
 //
-// HBM-bound streaming work. One wave (64 lanes) owns one row of width
-// 256*VEC (768 -> VEC 3, 1024 -> VEC 4); lane l holds elements 256c + 4l .. +3,
-// so every load/store instruction moves one contiguous 1 KiB (fp32) or 512 B
-// (bf16) segment of the row. Mean/variance/norms are wave-shuffle reductions
-// (rowmath.h: the fp32 row helpers shared with the backward kernels).
+// HBM-bound streaming work. One wave (64 lanes) owns one row in the wave-row layout of
+// rowmath.h, which holds the loads and stores for every storage type and the row helpers
+// shared with the backward, map and loss kernels; MX fp8 rows are written by mxfp8.h's rule.
+// Mean/variance/norms are wave-shuffle reductions.
 #include "common.h"
+#include "mxfp8.h"
 #include "rowmath.h"
 
 namespace {
-
-template <int VEC>
-__device__ __forceinline__ void load_any(const void* p, int dtype, float4_t (&v)[VEC], int lane) {
-  if (dtype == AACLIP_F32) {
-    load_row<VEC>((const float*)p, v, lane);
-  } else if (dtype == AACLIP_F16) {
-    const uint16_t* q = (const uint16_t*)p;
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) {
-      uint2 r = *(const uint2*)(q + 256 * c + 4 * lane);
-      v[c][0] = f16_to_f32((uint16_t)(r.x & 0xffff));
-      v[c][1] = f16_to_f32((uint16_t)(r.x >> 16));
-      v[c][2] = f16_to_f32((uint16_t)(r.y & 0xffff));
-      v[c][3] = f16_to_f32((uint16_t)(r.y >> 16));
-    }
-  } else {
-    const uint16_t* q = (const uint16_t*)p;
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) {
-      uint2 r = *(const uint2*)(q + 256 * c + 4 * lane);
-      v[c][0] = __uint_as_float(r.x << 16);
-      v[c][1] = __uint_as_float(r.x & 0xffff0000u);
-      v[c][2] = __uint_as_float(r.y << 16);
-      v[c][3] = __uint_as_float(r.y & 0xffff0000u);
-    }
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ void store_any(void* p, int dtype, const float4_t (&v)[VEC], int lane) {
-  if (dtype == AACLIP_F32) {
-    store_row<VEC>((float*)p, v, lane);
-  } else {
-    const bool h = dtype == AACLIP_F16;
-    uint16_t* q = (uint16_t*)p;
-#pragma unroll
-    for (int c = 0; c < VEC; ++c) {
-      uint2 r;
-      r.x = h ? pack_f16x2(v[c][0], v[c][1]) : pack_bf16x2(v[c][0], v[c][1]);
-      r.y = h ? pack_f16x2(v[c][2], v[c][3]) : pack_bf16x2(v[c][2], v[c][3]);
-      *(uint2*)(q + 256 * c + 4 * lane) = r;
-    }
-  }
-}
 
 // F.layer_norm: (x - mean) / sqrt(var + eps) * w + b, biased variance.
 template <int VEC>
@@ -72,20 +28,10 @@ __device__ __forceinline__ void layer_norm(const float4_t (&x)[VEC], const float
 
 __device__ __forceinline__ size_t esize(int dtype) { return dtype == AACLIP_F32 ? 4 : (dtype == AACLIP_FP8 ? 1 : 2); }
 
-// smallest e with amax * 2^-e <= 448 (largest finite e4m3): the e8m0 block scale
-__device__ __forceinline__ int mx_exp_row(float amax) {
-  if (!(amax > 0.f)) return 0;
-  int x;
-  (void)frexpf(amax, &x);  // amax = m * 2^x, m in [0.5, 1)
-  int e = x - 9;           // amax * 2^-e in [256, 512)
-  if (ldexpf(amax, -e) > 448.f) e += 1;
-  return max(min(e, 127), -126);
-}
-
-// MX fp8 row store (AACLIP_FP8 outputs, config C5): lane l holds elements 256c + 4l..+3,
-// so a 64-element block is 16 lanes: max over them (4 xor-shuffles inside the 16-lane
-// group), e8m0 scale, RNE to e4m3 after the exact 2^-e scaling; 4 bytes per lane and
-// chunk; the block's first lane writes the scale byte to sc[(blk/2)*ld_sc + row][blk%2].
+// MX fp8 row store (AACLIP_FP8 outputs, config C5; the format is mxfp8.h's): lane l holds
+// elements 256c + 4l..+3, so a 64-element block is 16 lanes: max over them (4 xor-shuffles
+// inside the 16-lane group); 4 bytes per lane and chunk; the block's first lane writes the
+// scale byte.
 template <int VEC>
 __device__ __forceinline__ void store_mx(uint8_t* q, uint8_t* sc, int64_t ld_sc, size_t row,
                                          const float4_t (&v)[VEC], int lane) {
@@ -94,15 +40,9 @@ __device__ __forceinline__ void store_mx(uint8_t* q, uint8_t* sc, int64_t ld_sc,
     float amax = fmaxf(fmaxf(fabsf(v[c][0]), fabsf(v[c][1])), fmaxf(fabsf(v[c][2]), fabsf(v[c][3])));
 #pragma unroll
     for (int o = 1; o < 16; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-    const int e = mx_exp_row(amax);
-    const float inv = __uint_as_float((uint32_t)(127 - e) << 23);
-    uint32_t w = __builtin_amdgcn_cvt_pk_fp8_f32(v[c][0] * inv, v[c][1] * inv, 0, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(v[c][2] * inv, v[c][3] * inv, w, true);
-    *(uint32_t*)(q + row * (256 * VEC) + 256 * c + 4 * lane) = w;
-    if ((lane & 15) == 0) {
-      const int blk = 4 * c + (lane >> 4);
-      sc[((size_t)(blk >> 1) * ld_sc + row) * 2 + (blk & 1)] = (uint8_t)(e + 127);
-    }
+    const int e = mx_exp(amax);
+    *(uint32_t*)(q + row * (256 * VEC) + 256 * c + 4 * lane) = mx_pack4(v[c][0], v[c][1], v[c][2], v[c][3], pow2i(-e));
+    if ((lane & 15) == 0) *mx_scale_ptr(sc, ld_sc, row, 4 * c + (lane >> 4)) = (uint8_t)(e + 127);
   }
 }
 
@@ -232,18 +172,7 @@ __global__ __launch_bounds__(256) void eot_ln_kernel(int out_dtype, const float*
   const int s = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (s >= n_seq) return;
   constexpr int D = 256 * VEC;
-  // argmax over the row, first occurrence (EOT = 49407 is the largest id)
-  int best_v = -2147483647 - 1, best_i = 0;
-  for (int t = lane; t < ctx; t += 64) {
-    int v = tokens[(size_t)s * ctx + t];
-    if (v > best_v) { best_v = v; best_i = t; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    int ov = __shfl_xor(best_v, o, 64);
-    int oi = __shfl_xor(best_i, o, 64);
-    if (ov > best_v || (ov == best_v && oi < best_i)) { best_v = ov; best_i = oi; }
-  }
+  const int best_i = eot_index(tokens, s, ctx, lane);
   float4_t v[VEC], o[VEC];
   load_row<VEC>(x + ((size_t)s * ctx + best_i) * D, v, lane);
   layer_norm<VEC>(v, w, b, o, lane);
@@ -453,10 +382,8 @@ __global__ __launch_bounds__(256) void quant_fp8_kernel(int in_dtype, const void
 }
 
 
-// MX variant: one wave per row, lane l owns elements 8l + 512c .. +7, so a 64-element
-// block is 8 consecutive lanes: max over them (3 xor-shuffles), power-of-two e8m0
-// scale, RNE to e4m3 after an exact 2^-e scaling.
-
+// MX variant (mxfp8.h): one wave per row, lane l owns elements 8l + 512c .. +7, so a
+// 64-element block is 8 consecutive lanes: max over them (3 xor-shuffles).
 __global__ __launch_bounds__(256) void quant_mx_kernel(int in_dtype, const void* __restrict__ x, int64_t ldx,
                                                        uint8_t* __restrict__ q, int64_t ldq,
                                                        uint8_t* __restrict__ sc, int64_t ld_sc, int rows, int cols) {
@@ -471,17 +398,11 @@ __global__ __launch_bounds__(256) void quant_mx_kernel(int in_dtype, const void*
     for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
 #pragma unroll
     for (int o = 1; o < 8; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-    const int e = mx_exp_row(amax);
-    const float inv = __uint_as_float((uint32_t)(127 - e) << 23);
-    uint32_t w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * inv, v[1] * inv, 0, false);
-    w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[2] * inv, v[3] * inv, w0, true);
-    uint32_t w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4] * inv, v[5] * inv, 0, false);
-    w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[6] * inv, v[7] * inv, w1, true);
-    *(uint2*)(q + (size_t)row * ldq + c0) = uint2{w0, w1};
-    if ((lane & 7) == 0) {
-      const int blk = c0 >> 6;
-      sc[((size_t)(blk >> 1) * ld_sc + row) * 2 + (blk & 1)] = (uint8_t)(e + 127);
-    }
+    const int e = mx_exp(amax);
+    const float inv = pow2i(-e);
+    *(uint2*)(q + (size_t)row * ldq + c0) =
+        uint2{mx_pack4(v[0], v[1], v[2], v[3], inv), mx_pack4(v[4], v[5], v[6], v[7], inv)};
+    if ((lane & 7) == 0) *mx_scale_ptr(sc, ld_sc, row, c0 >> 6) = (uint8_t)(e + 127);
   }
 }
 

@@ -21,6 +21,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "rowmath.h"  // the wave-row layout: load_row_as, load_anchors
 
 namespace {
 
@@ -276,15 +277,7 @@ __global__ __launch_bounds__(64) void patch_logits_bwd_kernel(const void* __rest
   const int lane = threadIdx.x, ch = blockIdx.x, b = blockIdx.y;
   const float* Tb = T + (size_t)b * t_stride;
   float4_t t0[3], t1[3];
-  if (df) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float* tp = Tb + 2 * (256 * c + 4 * lane);
-      const float4_t a = *(const float4_t*)tp, e = *(const float4_t*)(tp + 4);
-      t0[c] = float4_t{a[0], a[2], e[0], e[2]};
-      t1[c] = float4_t{a[1], a[3], e[1], e[3]};
-    }
-  }
+  if (df) load_anchors(Tb, t0, t1, lane);
   float4_t acc0[3] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}}, acc1[3] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
   const float* dg = dgrid + (size_t)b * 2 * group;
   const int p_end = min((ch + 1) * kRows, group);
@@ -294,19 +287,7 @@ __global__ __launch_bounds__(64) void patch_logits_bwd_kernel(const void* __rest
     const float d0 = dg[p], d1 = dg[group + p];
     if (partial) {
       float4_t v[3];
-      if constexpr (F32IN) {
-        const float* q = (const float*)f + row * ld;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c] = *(const float4_t*)(q + 256 * c + 4 * lane);
-      } else {
-        const uint16_t* q = (const uint16_t*)f + row * ld;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const uint2 r = *(const uint2*)(q + 256 * c + 4 * lane);
-          v[c] = float4_t{__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u),
-                          __uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u)};
-        }
-      }
+      load_row_as<F32IN, 3>(f, row * ld, v, lane);
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         acc0[c] += v[c] * d0;

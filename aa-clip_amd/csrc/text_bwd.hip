@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* dy, int
 }
 
 // Backward of eot_ln_kernel: row (s, t) of g is LN_bwd(dy[s]; x[s, t]) at t = the first
-// argmax of tokens[s], zero elsewhere. One wave per row; the argmax is rows.hip's.
+// argmax of tokens[s] (eot_index, the forward's), zero elsewhere. One wave per row.
 template <int VEC>
 __global__ __launch_bounds__(256) void eot_ln_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                          const int32_t* __restrict__ tokens,
@@ -136,17 +136,7 @@ __global__ __launch_bounds__(256) void eot_ln_bwd_kernel(const float* __restrict
   if (row >= rows) return;
   constexpr int D = 256 * VEC;
   const int s = row / ctx, t = row % ctx;
-  int best_v = -2147483647 - 1, best_i = 0;
-  for (int k = lane; k < ctx; k += 64) {
-    const int v = tokens[(size_t)s * ctx + k];
-    if (v > best_v) { best_v = v; best_i = k; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int ov = __shfl_xor(best_v, o, 64);
-    const int oi = __shfl_xor(best_i, o, 64);
-    if (ov > best_v || (ov == best_v && oi < best_i)) { best_v = ov; best_i = oi; }
-  }
+  const int best_i = eot_index(tokens, s, ctx, lane);
   float4_t o[VEC];
   if (t == best_i) {  // wave-uniform
     float4_t xv[VEC], dv[VEC];
@@ -169,24 +159,13 @@ __global__ __launch_bounds__(256) void act_kernel(int mode, const float* x, floa
   y[i] = mode == AACLIP_EPI_GELU ? gelu_erf(v) : mode == AACLIP_EPI_QGELU ? qgelu_exact(v) : leaky_relu(v);
 }
 
-// GELU / QuickGELU: ref = the pre-activation v. gelu'(v) = Phi(v) + v phi(v);
-// quick'(v) = s + 1.702 v s (1 - s), s = sigmoid(1.702 v). LeakyReLU: ref = the OUTPUT (its
-// sign is the input's); slope 1 above 0, 0.01 at and below 0 (torch's leaky_relu_backward).
+// dx = dy * act_slope(ref) (common.h): ref = the pre-activation for GELU / QuickGELU, the
+// OUTPUT for LeakyReLU.
 __global__ __launch_bounds__(256) void act_bwd_kernel(int mode, const float* dy, const float* ref, float* dx,
                                                       size_t n) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float v = ref[i];
-  float d;
-  if (mode == AACLIP_EPI_GELU) {
-    const float cdf = 0.5f * (1.0f + erff(v * 0.70710678118654752440f));
-    d = cdf + v * (0.39894228040143267794f * expf(-0.5f * v * v));
-  } else if (mode == AACLIP_EPI_QGELU) {
-    const float s = 1.0f / (1.0f + expf(-1.702f * v));
-    d = s + 1.702f * v * s * (1.0f - s);
-  } else {
-    d = v > 0.f ? 1.0f : 0.01f;
-  }
+  const float d = act_slope(mode, ref[i]);
   dx[i] = dy[i] * d;
 }
 
@@ -351,8 +330,6 @@ __global__ __launch_bounds__(256) void linear_wgrad_finalize_kernel(const float*
   for (int c = 0; c < nchunk; ++c) s += (double)partial[(size_t)c * nk + e];
   dW[(e / K) * lddw + e % K] = (float)s;
 }
-
-bool act_mode_ok(int mode) { return mode == AACLIP_EPI_GELU || mode == AACLIP_EPI_QGELU || mode == AACLIP_EPI_LEAKY; }
 
 }  // namespace
 

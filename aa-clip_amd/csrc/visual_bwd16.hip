@@ -37,21 +37,9 @@ __global__ __launch_bounds__(256) void act_to16_kernel(int mode, const float* __
   }
 }
 
-// aaclip_act_bwd's derivative (text_bwd.hip act_bwd_kernel) of the reference value v: the exact erf /
-// sigmoid forms. The forward's gelu_fast2 is within 2.6e-5 absolute of the erf form, an order below
-// the bf16 rounding of dx.
-__device__ __forceinline__ float act_slope(int mode, float v) {
-  if (mode == AACLIP_EPI_GELU) {
-    const float cdf = 0.5f * (1.0f + erff(v * 0.70710678118654752440f));
-    return cdf + v * (0.39894228040143267794f * expf(-0.5f * v * v));
-  }
-  if (mode == AACLIP_EPI_QGELU) {
-    const float s = 1.0f / (1.0f + expf(-1.702f * v));
-    return s + 1.702f * v * s * (1.0f - s);
-  }
-  return v > 0.f ? 1.0f : 0.01f;
-}
-
+// The derivative is aaclip_act_bwd's (common.h act_slope: the exact erf / sigmoid forms). The
+// forward's gelu_fast2 is within 2.6e-5 absolute of the erf form, an order below the bf16
+// rounding of dx.
 template <bool H16>
 __global__ __launch_bounds__(256) void act_bwd16_kernel(int mode, const uint16_t* dy, const float* __restrict__ ref,
                                                         uint16_t* dx, size_t n) {
@@ -112,10 +100,6 @@ __global__ __launch_bounds__(256) void cast_rows_up_kernel(const uint16_t* __res
 }
 
 inline bool is16(int dtype) { return dtype == AACLIP_BF16 || dtype == AACLIP_F16; }
-inline bool act_mode_ok(int mode) {
-  return mode == AACLIP_EPI_GELU || mode == AACLIP_EPI_QGELU || mode == AACLIP_EPI_LEAKY;
-}
-
 }  // namespace
 
 extern "C" int aaclip_act_to16(int mode, const float* x, void* y, int out_dtype, int64_t n, void* stream) {

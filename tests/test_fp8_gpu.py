@@ -169,6 +169,48 @@ def test_quant_fp8_mx(dev, dtype, rows, cols):
     assert ((deq - xf).abs() <= 2.0 ** -4 * xf.abs() + step * 2.0 ** -9).all()
 
 
+def _mx_edge_rows():
+    """fp32 [12, 128]: block 0 of row i holds v_i, -0.37 v_i, v_i / 3, block 1 is zero. The v_i sit
+    on the edges of the exponent rule (csrc/mxfp8.h); none of the entries is subnormal."""
+    top = torch.tensor(448.0 * 2 ** 5, dtype=torch.float32)
+    v = torch.tensor([0.0, 448.0, 449.0, 447.9, 256.0, 1.0, top, torch.nextafter(top, torch.tensor(float("inf"))),
+                      2.0 ** -120, 448.0 * 2.0 ** -126, 3e38, 2.0 ** 127], dtype=torch.float32)
+    x = torch.zeros(12, 128, dtype=torch.float32)
+    x[:, 0], x[:, 1], x[:, 2] = v, -0.37 * v, v / 3
+    return x
+
+
+def _mx_rule_ref(x):
+    """The exponent rule and the codes restated in float64: e = the smallest integer with
+    amax * 2^-e <= 448 per 64-column block, clamped to [-126, 127], 0 for a zero block;
+    codes = e4m3(x * 2^-e). Returns (e [rows, cols/64] int64, codes [rows, cols] uint8)."""
+    rows, cols = x.shape
+    xd = x.double()
+    amax = xd.abs().view(rows, cols // 64, 64).amax(-1)
+    _, ex = torch.frexp(amax)  # amax = m 2^ex, m in [0.5, 1)
+    e = ex.long() - 9          # amax 2^-e in [256, 512)
+    e = e + (amax * torch.pow(2.0, -e.double()) > 448).long()
+    e = torch.where(amax > 0, e.clamp(-126, 127), torch.zeros_like(e))
+    scaled = xd * torch.pow(2.0, -e.double()).repeat_interleave(64, dim=1)
+    return e, scaled.float().to(FP8).view(torch.uint8)
+
+
+def test_mx_exponent_rule_edges(dev):
+    """aaclip_quant_fp8_mx on block maxima at the edges of the rule: at, just above and just below
+    448 2^k, the clamp at e = -126, the largest fp32 magnitudes, an all-zero block and row. Scale
+    bytes and e4m3 codes equal the float64 restatement."""
+    x = _mx_edge_rows()
+    e_ref, code_ref = _mx_rule_ref(x)
+    # the restatement itself, on the values worked out by hand
+    assert e_ref[:, 0].tolist() == [0, 0, 1, 0, 0, -8, 5, 6, -126, -126, 120, 119]
+    assert code_ref[1, 0] == 126 and code_ref[2, 0] == 118 and (e_ref[:, 1] == 0).all()
+    q = torch.empty(12, 128, device=dev, dtype=FP8)
+    sc = ops.mx_scales(12, 128, dev, ld=12)
+    ops.quant_fp8_mx(x.to(dev), q, sc)
+    assert torch.equal(sc[0].cpu().long() - 127, e_ref)
+    assert torch.equal(q.cpu().view(torch.uint8), code_ref)
+
+
 # K = 128 / 256 / 384: nk = 1, 2 (the steady-state loop runs zero times: the prologue hands
 # straight to the counted nk-2 tail) and 3 (odd) K-steps of 128
 @pytest.mark.parametrize("M,N,K", [(1154, 3072, 1024), (37, 1024, 4096), (577 * 3, 768 + 256, 1024), (300, 256, 128),
