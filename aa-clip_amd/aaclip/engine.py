@@ -256,8 +256,9 @@ def _block_bwd(g, blk: dict, bt: dict, sv: dict, attend_bwd, act_mode: str, d_qk
 
 class MemoryBank:
     """The few-shot memory bank of one class (VisualEngine.build_bank): levels, a list of L device
-    tensors [shots * P, 768] of unit patch rows; img_size and dtype, which a predict_few_shot call
-    must match; shots, the number of support images."""
+    tensors [shots * P, 768] of unit patch rows (dtype float8_e4m3fn: of ops.Fp8MxRows, the rows in
+    MX fp8 with their block scales and reciprocal norms); img_size and dtype, which a
+    predict_few_shot call must match; shots, the number of support images."""
 
     def __init__(self, levels: list, img_size: int, dtype: torch.dtype, shots: int):
         self.levels, self.img_size, self.dtype, self.shots = list(levels), int(img_size), dtype, int(shots)
@@ -858,12 +859,32 @@ class VisualEngine:
         parts = [self._unit_rows(self.forward_raw(x[b0:min(B, b0 + mc)])[0]) for b0 in range(0, B, mc)]
         return parts[0] if len(parts) == 1 else [torch.cat(lv) for lv in zip(*parts)]
 
-    def build_bank(self, support_images: torch.Tensor) -> "MemoryBank":
+    @torch.no_grad()
+    @_on_device
+    def bank_rows_fp8mx(self, x: torch.Tensor):
+        """The level features of x as unit rows in MX fp8: list[L] of ops.Fp8MxRows [B*P, 768]. The
+        chunks' raw rows are joined ahead of the quantisation, so a level has one scale buffer."""
+        B, S = x.shape[0], x.shape[-1]
+        mc = self.max_chunk(S)
+        if B <= mc:
+            return [ops.unit_rows_fp8mx(s_) for s_ in self.forward_raw(x)[0]]
+        parts = [[s_.clone() for s_ in self.forward_raw(x[b0:min(B, b0 + mc)])[0]] for b0 in range(0, B, mc)]
+        return [ops.unit_rows_fp8mx(torch.cat(lv)) for lv in zip(*parts)]
+
+    def build_bank(self, support_images: torch.Tensor, search_dtype=None) -> "MemoryBank":
         """The memory bank of k normal support images [k, 3, S, S] (reference test.py:39-50,
-        get_support_features): per level the k*P unit patch rows, in search_dtype."""
+        get_support_features): per level the k*P unit patch rows, in search_dtype. search_dtype
+        torch.float8_e4m3fn (any engine mode) keeps them in MX fp8 instead, half the bytes, for the
+        block-scaled fp8 search; None is the engine's own."""
         _check_image(support_images)
         if support_images.shape[0] < 1:
             raise ValueError("build_bank needs at least one support image")
+        if search_dtype is not None and search_dtype not in (self.search_dtype, torch.float8_e4m3fn):
+            raise ValueError(f"build_bank: search_dtype must be None, {self.search_dtype} (this engine's) or "
+                             f"torch.float8_e4m3fn, got {search_dtype}")
+        if search_dtype == torch.float8_e4m3fn:
+            return MemoryBank(self.bank_rows_fp8mx(support_images), int(support_images.shape[-1]),
+                              torch.float8_e4m3fn, int(support_images.shape[0]))
         return MemoryBank(self.bank_rows(support_images), int(support_images.shape[-1]), self.search_dtype,
                           int(support_images.shape[0]))
 
@@ -874,15 +895,19 @@ class VisualEngine:
         fp32, fresh tensors. zs_map / zs_score are predict()'s quantities from the projected rows (the
         row path of _tail: the few-shot search needs the rows, so not the partials form). fs_map: per
         level each patch's 1 - max cosine against the bank's rows of that level (ops.bank_nn +
-        ops.bank_distance), summed over the levels, then the domain's blur + upsample. Eager, on the
-        current stream."""
+        ops.bank_distance), summed over the levels, then the domain's blur + upsample. A
+        float8_e4m3fn bank (build_bank(..., torch.float8_e4m3fn)) is searched in MX fp8: the level
+        rows go through ops.unit_rows_fp8mx and ops.bank_nn_fp8mx. Eager, on the current stream."""
         _check_image(x)
         B, S = x.shape[0], x.shape[-1]
         if not isinstance(bank, MemoryBank) or len(bank.levels) != len(self.levels):
             raise ValueError(f"bank must be a MemoryBank of {len(self.levels)} levels (build_bank)")
-        if bank.img_size != S or bank.dtype != self.search_dtype:
+        fp8 = bank.dtype == torch.float8_e4m3fn
+        if bank.img_size != S or not (fp8 or bank.dtype == self.search_dtype):
             raise ValueError(f"the bank was built at {bank.img_size} px in {bank.dtype}; this call is at {S} px in "
                              f"{self.search_dtype}: rebuild it (build_bank)")
+        if any(isinstance(lv, ops.Fp8MxRows) != fp8 for lv in bank.levels):
+            raise ValueError(f"the bank's levels do not hold its dtype {bank.dtype}: rebuild it (build_bank)")
         T = T.to(self.device, torch.float32).contiguous()
         k, s = _blur_for(domain)
         zs_map = torch.empty(B, S, S, device=self.device, dtype=torch.float32)
@@ -896,9 +921,14 @@ class VisualEngine:
             g = ws["g"]
             grid = torch.empty(b1 - b0, 1, g, g, device=self.device, dtype=torch.float32)
             part = None
-            for j, (q, r) in enumerate(zip(self._unit_rows(seg_raw), bank.levels)):
-                part = ops.bank_nn(q, r, part)
-                ops.bank_distance(part, grid, accumulate=j > 0)
+            if fp8:
+                for j, (s_, r) in enumerate(zip(seg_raw, bank.levels)):
+                    part = ops.bank_nn_fp8mx(ops.unit_rows_fp8mx(s_), r, part)
+                    ops.bank_distance(part, grid, accumulate=j > 0)
+            else:
+                for j, (q, r) in enumerate(zip(self._unit_rows(seg_raw), bank.levels)):
+                    part = ops.bank_nn(q, r, part)
+                    ops.bank_distance(part, grid, accumulate=j > 0)
             ops.blur_upsample(grid, fs_map[b0:b1].view(b1 - b0, 1, S, S), ksize=k, sigma=s)
         return zs_map, zs_score, fs_map
 

@@ -1586,6 +1586,96 @@ def bank_nn(q, bank, part=None):
     return part
 
 
+class Fp8MxRows:
+    """Unit rows in MX fp8, the operands of bank_nn_fp8mx (unit_rows_fp8mx): q uint8 [n, K], the e4m3
+    bytes; sc uint8 [K / 128, ld, 2], the e8m0 block scales (mx_scales; ld even); rnorm fp32 [n], the
+    reciprocal norm of each stored row. shape is q's, dtype torch.float8_e4m3fn."""
+    dtype = torch.float8_e4m3fn
+
+    def __init__(self, q, sc, rnorm):
+        self.q, self.sc, self.rnorm = q, sc, rnorm
+
+    @property
+    def shape(self):
+        return self.q.shape
+
+    @property
+    def device(self):
+        return self.q.device
+
+    def __repr__(self):
+        return f"Fp8MxRows(shape={tuple(self.q.shape)}, ld_sc={self.sc.shape[1]})"
+
+
+def unit_rows_fp8mx(x):
+    """The rows of x [n, K] (float32, bfloat16 or float16; unit column stride, 16-byte aligned rows; K a
+    multiple of 128) L2-normalised as l2_normalize does it and MX-quantised to e4m3 by csrc/mxfp8.h's
+    rule, with the reciprocal norm of every stored row (aaclip_unit_rows_fp8mx). Returns a fresh
+    Fp8MxRows."""
+    _rowmajor(x, "x")
+    tag = dtag(x)
+    n, K = x.shape
+    if n < 1 or K == 0 or K % 128:
+        raise ValueError(f"unit_rows_fp8mx needs x [n >= 1, K] with K a multiple of 128, got {tuple(x.shape)}")
+    if x.stride(0) < K or (x.stride(0) * x.element_size()) % 16 or x.data_ptr() % 16:
+        raise ValueError("unit_rows_fp8mx: x's rows must be 16-byte aligned, with a row stride of at least K")
+    _dev(x)
+    q = torch.empty(n, K, device=x.device, dtype=torch.uint8)
+    sc = mx_scales(n, K, x.device)
+    rnorm = torch.empty(n, device=x.device, dtype=torch.float32)
+    _launch("fewshot", "unit_rows_fp8mx", 4.0 * n * K, n * K * (x.element_size() + 1.0) + 4.0 * n,
+            "aaclip_unit_rows_fp8mx", tag, _ptr(x), x.stride(0), _ptr(q), q.stride(0), _ptr(sc), sc.shape[1],
+            _ptr(rnorm), n, K, _stream())
+    return Fp8MxRows(q, sc, rnorm)
+
+
+def _mx_rows(t, name):
+    if not isinstance(t, Fp8MxRows):
+        raise TypeError(f"bank_nn_fp8mx: {name} must be an Fp8MxRows (unit_rows_fp8mx), got {type(t).__name__}")
+    q, sc, rn = t.q, t.sc, t.rnorm
+    _rowmajor(q, name)
+    n, K = q.shape
+    if n < 1:
+        raise ValueError(f"bank_nn_fp8mx: {name} has no rows")
+    if q.dtype not in (torch.uint8, torch.float8_e4m3fn):
+        raise TypeError(f"bank_nn_fp8mx: {name}.q must hold e4m3 bytes (uint8 or float8_e4m3fn), got {q.dtype}")
+    if q.stride(0) < K or q.stride(0) % 16 or q.data_ptr() % 16:
+        raise ValueError(f"bank_nn_fp8mx: {name}'s rows must be 16-byte aligned, with a row stride of at least K")
+    if (sc.dtype != torch.uint8 or sc.dim() != 3 or not sc.is_contiguous() or sc.shape[0] * 128 != K
+            or sc.shape[1] < n or sc.shape[1] % 2 or sc.shape[2] != 2):
+        raise ValueError(f"bank_nn_fp8mx: {name}.sc must be contiguous uint8 [K / 128, ld >= rows and even, 2], got "
+                         f"{sc.dtype} {tuple(sc.shape)}")
+    if rn.dtype != torch.float32 or tuple(rn.shape) != (n,) or not rn.is_contiguous():
+        raise ValueError(f"bank_nn_fp8mx: {name}.rnorm must be contiguous float32 [{n}], got {rn.dtype} "
+                         f"{tuple(rn.shape)}")
+
+
+def bank_nn_fp8mx(q, bank, part=None):
+    """bank_nn on MX fp8 operands (aaclip_bank_nn_fp8mx): part[m, s] = max over the bank rows of split s
+    of the cosine between the stored rows, (q^[m] . bank^[n]) * bank.rnorm[n] * q.rnorm[m], on the
+    block-scaled fp8 MFMA. q, bank: Fp8MxRows of one K, a multiple of 128 (any 16-byte aligned row
+    stride). part as in bank_nn, with bank_nn_plan's layout; bank_distance takes it as it is."""
+    _mx_rows(q, "q")
+    _mx_rows(bank, "bank")
+    M, K = q.shape
+    Nb = bank.shape[0]
+    if bank.shape[1] != K or K % 128 or K == 0:
+        raise ValueError(f"bank_nn_fp8mx needs q [M, K] and bank [Nb, K] with K a multiple of 128, got "
+                         f"{tuple(q.shape)} and {tuple(bank.shape)}")
+    n_splits, _ = bank_nn_plan(M, Nb)
+    if part is None:
+        part = torch.empty(M, n_splits, device=q.device, dtype=torch.float32)
+    if part.dtype != torch.float32 or tuple(part.shape) != (M, n_splits) or not part.is_contiguous():
+        raise ValueError(f"bank_nn_fp8mx: part must be a contiguous float32 {(M, n_splits)} workspace, got "
+                         f"{part.dtype} {tuple(part.shape)}")
+    _dev(q.q, q.sc, q.rnorm, bank.q, bank.sc, bank.rnorm, part)
+    _launch("fewshot", "bank_nn_fp8mx", 2.0 * M * Nb * K, (M + Nb) * (K + K / 64 + 4.0) + 4.0 * part.numel(),
+            "aaclip_bank_nn_fp8mx", M, Nb, K, _ptr(q.q), q.q.stride(0), _ptr(q.sc), q.sc.shape[1], _ptr(q.rnorm),
+            _ptr(bank.q), bank.q.stride(0), _ptr(bank.sc), bank.sc.shape[1], _ptr(bank.rnorm), _ptr(part),
+            part.numel() * 4, _stream())
+    return part
+
+
 def bank_distance(part, grid, *, accumulate: bool):
     """grid[m] = (accumulate ? grid[m] : 0) + (1 - max_s part[m, s]) (aaclip_bank_distance). part fp32
     [M, n_splits] contiguous (bank_nn); grid contiguous fp32 of M elements, e.g. the [B, 1, g, g] grid

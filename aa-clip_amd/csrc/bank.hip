@@ -26,6 +26,9 @@
 //             alone or in a batch, and under any permutation of the bank.
 //             fp32 operands (the parity mode): v_mfma_f32_16x16x4_f32 on register-staged
 //             256 x 256 x 16 tiles, the same tile walk, splits and reductions.
+//             MX fp8 operands (aaclip_bank_nn_fp8mx, opt-in): the 16-bit kernel's staging and tile
+//             walk at a K-step of 128 on the block-scaled fp8 MFMA, the result the exact cosine
+//             between the stored rows (see bank_nn_mx_kernel).
 //   combine   aaclip_bank_distance: grid[m] = (accumulate ? grid[m] : 0) + (1 - max_s part[m][s]).
 //   fusion    aaclip_fewshot_fuse: class-normalised zero-shot + few-shot maps and scores, every
 //             operation a rounded fp32 one (tests/fewshot_ref.py states it in numpy float32).
@@ -66,9 +69,11 @@ __device__ __forceinline__ void fold_tile(float4_t (&acc)[RM][RN], float (&rmax)
 }
 
 // rows of the block tile: across the four lanes that share a row (fq), then across the WN
-// wave columns through `red` (WN * BM floats of LDS nobody reads any more), then out
+// wave columns through `red` (WN * BM floats of LDS nobody reads any more), then out; SCALED: times
+// the row's positive factor row_scale[m] (it commutes with the maxima, rounding included)
+template <bool SCALED = false>
 __device__ __forceinline__ void store_rows(const BankArgs& a, const float (&rmax)[RM], float* red, int m0, int split,
-                                           int wm, int wn, int lane) {
+                                           int wm, int wn, int lane, const float* row_scale = nullptr) {
   const int fr = lane & 15, fq = lane >> 4;
 #pragma unroll
   for (int i = 0; i < RM; ++i) {
@@ -83,6 +88,7 @@ __device__ __forceinline__ void store_rows(const BankArgs& a, const float (&rmax
     float v = red[r];
 #pragma unroll
     for (int w = 1; w < WN; ++w) v = fmaxf(v, red[w * BM + r]);
+    if constexpr (SCALED) v *= row_scale[m0 + r];
     a.part[(size_t)(m0 + r) * a.n_splits + split] = v;
   }
 }
@@ -93,6 +99,42 @@ constexpr int A_LOADS = A_BYTES / (NWAVES * 1024), B_LOADS = B_BYTES / (NWAVES *
 constexpr int kLds16 = 2 * STAGE_BYTES;
 static_assert(A_LOADS * NWAVES * 1024 == A_BYTES && B_LOADS * NWAVES * 1024 == B_BYTES, "tile");
 static_assert(WN * BM * (int)sizeof(float) <= STAGE_BYTES, "the row reduction reuses a stage");
+
+// global -> LDS of one K-step of the query tile and a bank tile, 128 bytes per row (64 16-bit
+// or 128 fp8 elements of ES bytes): per-lane DMA sources (row r = piece * 8 + lane / 8 of the
+// tile, physical 16-B chunk p = lane % 8 holds logical chunk p ^ (r & 7)); rows past the end are
+// the last row
+template <int ES>
+struct TileDma {
+  const char* Rg;
+  const char* q_src[A_LOADS];
+  int b_row[B_LOADS], b_col[B_LOADS];
+  __device__ __forceinline__ TileDma(const BankArgs& a, int m0, int wid, int lane) : Rg((const char*)a.R) {
+#pragma unroll
+    for (int i = 0; i < A_LOADS; ++i) {
+      const int r = (i * NWAVES + wid) * 8 + (lane >> 3);
+      q_src[i] = (const char*)a.Q + (size_t)min(m0 + r, a.M - 1) * a.ldq * ES + (((lane & 7) ^ (r & 7)) << 4);
+    }
+#pragma unroll
+    for (int i = 0; i < B_LOADS; ++i) {
+      b_row[i] = (i * NWAVES + wid) * 8 + (lane >> 3);
+      b_col[i] = ((lane & 7) ^ (b_row[i] & 7)) << 4;
+    }
+  }
+  // K-step kt of the query tile and of the bank tile at row n0 into the stage at base
+  __device__ __forceinline__ void stage(const BankArgs& a, char* base, int n0, int kt, int wid) const {
+#pragma unroll
+    for (int i = 0; i < A_LOADS; ++i)
+      __builtin_amdgcn_global_load_lds((const void*)(q_src[i] + kt * 128), LDS_PTR(base + (i * NWAVES + wid) * 1024),
+                                       16, 0, 0);
+#pragma unroll
+    for (int i = 0; i < B_LOADS; ++i) {
+      const char* src = Rg + (size_t)min(n0 + b_row[i], a.Nb - 1) * a.ldr * ES + b_col[i] + kt * 128;
+      __builtin_amdgcn_global_load_lds((const void*)src, LDS_PTR(base + A_BYTES + (i * NWAVES + wid) * 1024), 16, 0,
+                                       0);
+    }
+  }
+};
 
 template <bool H16>
 __global__ __launch_bounds__(NWAVES * 64) void bank_nn16_kernel(BankArgs a) {
@@ -106,35 +148,8 @@ __global__ __launch_bounds__(NWAVES * 64) void bank_nn16_kernel(BankArgs a) {
   const int nt = min(a.tiles_per_split, a.tiles_n - t0);  // >= 1: no split is empty (bank_plan)
   const int nk = a.K / 64;
 
-  // per-lane DMA sources (row r = piece * 8 + lane / 8 of the tile, physical 16-B chunk
-  // p = lane % 8 holds logical chunk p ^ (r & 7)); rows past the end are the last row
-  const char* __restrict__ Rg = (const char*)a.R;
-  const char* q_src[A_LOADS];
-  int b_row[B_LOADS], b_col[B_LOADS];
-#pragma unroll
-  for (int i = 0; i < A_LOADS; ++i) {
-    const int r = (i * NWAVES + wid) * 8 + (lane >> 3);
-    q_src[i] = (const char*)a.Q + (size_t)min(m0 + r, a.M - 1) * a.ldq * 2 + (((lane & 7) ^ (r & 7)) << 4);
-  }
-#pragma unroll
-  for (int i = 0; i < B_LOADS; ++i) {
-    b_row[i] = (i * NWAVES + wid) * 8 + (lane >> 3);
-    b_col[i] = ((lane & 7) ^ (b_row[i] & 7)) << 4;
-  }
-  auto stage = [&](int t, int kt, int buf) {
-    char* base = smem + buf * STAGE_BYTES;
-    const int n0 = (t0 + t) * BN;
-#pragma unroll
-    for (int i = 0; i < A_LOADS; ++i)
-      __builtin_amdgcn_global_load_lds((const void*)(q_src[i] + kt * 128), LDS_PTR(base + (i * NWAVES + wid) * 1024),
-                                       16, 0, 0);
-#pragma unroll
-    for (int i = 0; i < B_LOADS; ++i) {
-      const char* src = Rg + (size_t)min(n0 + b_row[i], a.Nb - 1) * a.ldr * 2 + b_col[i] + kt * 128;
-      __builtin_amdgcn_global_load_lds((const void*)src, LDS_PTR(base + A_BYTES + (i * NWAVES + wid) * 1024), 16, 0,
-                                       0);
-    }
-  };
+  const TileDma<2> dma(a, m0, wid, lane);
+  auto stage = [&](int t, int kt, int buf) { dma.stage(a, smem + buf * STAGE_BYTES, (t0 + t) * BN, kt, wid); };
 
   // fragment read offsets within a stage: 16-B chunk kk * 4 + fq of the row, swizzle undone
   const int fr = lane & 15, fq = lane >> 4;
@@ -255,6 +270,159 @@ __global__ __launch_bounds__(NWAVES * 64) void bank_nn32_kernel(BankArgs a) {
   store_rows(a, rmax, red, m0, split, wm, wn, lane);
 }
 
+// ============================================================== MX fp8 operands (mxfp8.h)
+// part[m][s] = max_n (Q^[m] . R^[n]) * r_rnorm[n] * q_rnorm[m]: the cosine between the fp8 MX
+// representations, norms included. A 128-column K-step of e4m3 is the 128-byte row the 16-bit
+// kernel stages, so the tile staging, the swizzle and the flat (tile, K-step) pipeline are its own;
+// a lane's fragment is the row's chunks fq and 4 + fq (the two chunk offsets the 16-bit kernel
+// reads one per half step), and v_mfma_scale_f32_16x16x128_f8f6f4 applies both operands' e8m0
+// block scales: lane group fq supplies the scale of K 32 fq .. 32 fq + 31, which lies in the
+// row's 64-block fq / 2. The scale pairs of a K-step's 256 + 256 rows (1 KiB) ride with the tile
+// behind the two stages: one dword LDS-DMA per lane of waves 0-1 (query rows) and 2-3 (bank rows),
+// contiguous in the [K / 128][ld][2] layout. At a ragged edge the dword's source is clamped into
+// the buffer and the lane reads the scale of the row its clamped tile row duplicates, so a
+// duplicate stays a duplicate. The bank row's reciprocal norm multiplies the accumulator ahead of
+// the running maximum (it differs per column; waves 4-7 bring a tile's 256 of them into LDS with
+// its first K-step), the query row's once at the end.
+typedef __attribute__((ext_vector_type(8))) int i32x8_t;
+typedef __attribute__((ext_vector_type(4))) int i32x4_t;
+
+struct BankMxArgs {
+  BankArgs b;  // Q, R: e4m3 bytes
+  const uint8_t* q_sc;
+  const uint8_t* r_sc;
+  const float* q_rnorm;
+  const float* r_rnorm;
+  int64_t ld_qsc, ld_rsc;
+};
+
+constexpr int SC_BYTES = (BM + BN) * 2;  // per stage: the query rows' scale pairs, then the bank rows'
+constexpr int RN_BYTES = BN * 4;         // per bank tile: its rows' reciprocal norms
+// Three norm slots, tile t in slot t % 3. Tile t + 1's norms are issued no earlier than tile t's
+// first K-step, and with a single K-step per tile (K = 128) tile t + 2's are issued during tile
+// t + 1's, straight after the wave's own fold of tile t with no barrier in between: slot
+// (t + 2) % 3 was last read by the fold of tile t - 1, which every wave has left behind at the
+// barrier that closed tile t. Two slots would let a fast wave overwrite what a slow one still folds.
+constexpr int RN_SLOTS = 3;
+constexpr int kLdsMx = 2 * STAGE_BYTES + 2 * SC_BYTES + RN_SLOTS * RN_BYTES;
+static_assert(BM * 2 == 2 * 64 * 4 && BN * 2 == 2 * 64 * 4 && RN_BYTES == 4 * 64 * 4,
+              "a dword per lane: two waves move either operand's scale pairs, four the norms");
+
+// rmax[i] = max(rmax[i], the lane's 16 values of tile row i, each times its bank row's rn:
+// rn[j] = the reciprocal norms of bank columns 4 fq .. 4 fq + 3 of column tile j)
+__device__ __forceinline__ void fold_tile_scaled(float4_t (&acc)[RM][RN], const float4_t* rn, float (&rmax)[RM]) {
+#pragma unroll
+  for (int j = 0; j < RN; ++j) {
+    const float4_t f = rn[4 * j];  // 16 columns on
+#pragma unroll
+    for (int i = 0; i < RM; ++i) {
+      const float4_t v = acc[i][j] * f;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) rmax[i] = fmaxf(rmax[i], v[e]);
+      acc[i][j] = float4_t{0.f, 0.f, 0.f, 0.f};
+    }
+  }
+}
+
+__global__ __launch_bounds__(NWAVES * 64) void bank_nn_mx_kernel(BankMxArgs x) {
+  const BankArgs& a = x.b;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wm = wid / WN, wn = wid % WN;
+  const int split = blockIdx.x % a.n_splits, m0 = (blockIdx.x / a.n_splits) * BM;
+  const int t0 = split * a.tiles_per_split;
+  const int nt = min(a.tiles_per_split, a.tiles_n - t0);
+  const int nk = a.K / 128;
+
+  const TileDma<1> dma(a, m0, wid, lane);
+  // scale DMA (waves 0-1 the query rows', 2-3 the bank rows'): the lane's dword is the pairs of
+  // tile rows sp and sp + 1; ld is even and at least the row count, so the clamped source stays
+  // inside the buffer and every real row keeps its own. Waves 4-7 bring a bank tile's 256
+  // reciprocal norms with its first K-step, a row past the end being the last row again.
+  const int sp = ((wid & 1) * 64 + lane) * 2;
+  const uint8_t* qs_src = x.q_sc + min((int64_t)m0 + sp, x.ld_qsc - 2) * 2;
+  char* const sc_lds = smem + 2 * STAGE_BYTES;
+  char* const rn_lds = sc_lds + 2 * SC_BYTES;
+  auto stage = [&](int t, int kt, int buf, bool first) {
+    const int n0 = (t0 + t) * BN;
+    if (wid < 2) {
+      __builtin_amdgcn_global_load_lds((const void*)(qs_src + (int64_t)kt * x.ld_qsc * 2),
+                                       LDS_PTR(sc_lds + buf * SC_BYTES + wid * 256), 4, 0, 0);
+    } else if (wid < 4) {
+      const uint8_t* src = x.r_sc + ((int64_t)kt * x.ld_rsc + min((int64_t)n0 + sp, x.ld_rsc - 2)) * 2;
+      __builtin_amdgcn_global_load_lds((const void*)src, LDS_PTR(sc_lds + buf * SC_BYTES + BM * 2 + (wid - 2) * 256),
+                                       4, 0, 0);
+    } else if (first) {
+      const float* src = x.r_rnorm + min(n0 + (wid - 4) * 64 + lane, a.Nb - 1);
+      __builtin_amdgcn_global_load_lds((const void*)src, LDS_PTR(rn_lds + (t % RN_SLOTS) * RN_BYTES + (wid - 4) * 256), 4, 0,
+                                       0);
+    }
+    dma.stage(a, smem + buf * STAGE_BYTES, n0, kt, wid);
+  };
+
+  // fragment of tile row r0 + 16 i (r0 % 16 == fr): chunks fq and 4 + fq of the row, swizzle undone
+  // (r & 7 == fr & 7 for every i, and the two chunk numbers differ in bit 2, so every offset is one
+  // of two lane values plus a constant). The row's scale byte is the one of its block fq / 2; a
+  // clamped query row is never stored, so it may read whatever scale its tile row has.
+  const int fr = lane & 15, fq = lane >> 4;
+  const int ch0 = (fq ^ (fr & 7)) << 4;
+  const int a_off = (wm * TM + fr) * 128 + ch0, b_off = A_BYTES + (wn * TN + fr) * 128 + ch0;
+  const int qs_off = (wm * TM + fr) * 2 + (fq >> 1);
+  auto frag = [&](const char* p, int off) {  // off ^ 64: chunk 4 + fq (bit 6 of off is the chunk's bit 2)
+    const i32x4_t lo = *(const i32x4_t*)(p + off), hi = *(const i32x4_t*)(p + (off ^ 64));
+    return i32x8_t{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+  };
+
+  float4_t acc[RM][RN];
+  float rmax[RM];
+#pragma unroll
+  for (int i = 0; i < RM; ++i) {
+    rmax[i] = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < RN; ++j) acc[i][j] = float4_t{0.f, 0.f, 0.f, 0.f};
+  }
+
+  stage(0, 0, 0, true);
+  __syncthreads();
+  int cur = 0;
+  for (int t = 0; t < nt; ++t) {
+    // where the scale pairs of the lane's bank rows lie: a tile row past the end duplicates the
+    // last row, and takes its scales
+    int bs_off[RN];
+#pragma unroll
+    for (int j = 0; j < RN; ++j)
+      bs_off[j] = BM * 2 + min(wn * TN + j * 16 + fr, a.Nb - 1 - (t0 + t) * BN) * 2 + (fq >> 1);
+    for (int kt = 0; kt < nk; ++kt) {
+      if (kt + 1 < nk)
+        stage(t, kt + 1, cur ^ 1, false);
+      else if (t + 1 < nt)
+        stage(t + 1, 0, cur ^ 1, true);
+      const char* base = smem + cur * STAGE_BYTES;
+      const char* scb = sc_lds + cur * SC_BYTES;
+      i32x8_t bf[RN];
+      int sb[RN];
+#pragma unroll
+      for (int j = 0; j < RN; ++j) {
+        bf[j] = frag(base + j * 2048, b_off);
+        sb[j] = *(const uint8_t*)(scb + bs_off[j]);
+      }
+#pragma unroll
+      for (int i = 0; i < RM; ++i) {
+        const i32x8_t af = frag(base + i * 2048, a_off);
+        const int sq = *(const uint8_t*)(scb + qs_off + i * 32);
+#pragma unroll
+        for (int j = 0; j < RN; ++j)  // formats 0/0 = e4m3/e4m3; bank block scale, query block scale; C^T tile
+          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(bf[j], af, acc[i][j], 0, 0, 0, sb[j], 0, sq);
+      }
+      __syncthreads();
+      cur ^= 1;
+    }
+    fold_tile_scaled(acc, (const float4_t*)(rn_lds + (t % RN_SLOTS) * RN_BYTES) + (wn * TN) / 4 + fq, rmax);
+  }
+  store_rows<true>(a, rmax, (float*)smem, m0, split, wm, wn, lane, x.q_rnorm);
+}
+
 // ============================================================== combine, fusion
 __global__ __launch_bounds__(MT) void bank_distance_kernel(const float* __restrict__ part, int M, int n_splits,
                                                            int accumulate, float* __restrict__ grid) {
@@ -346,6 +514,29 @@ extern "C" int aaclip_bank_nn(int dtype, int M, int Nb, int K, const void* Q, in
     const int rc = dtype == AACLIP_F16 ? launch16<true>(a, (int)blocks, s) : launch16<false>(a, (int)blocks, s);
     if (rc != AACLIP_OK) return rc;
   }
+  AACLIP_CHECK_LAUNCH();
+  return AACLIP_OK;
+}
+
+extern "C" int aaclip_bank_nn_fp8mx(int M, int Nb, int K, const void* Q, int64_t ldq, const void* q_sc, int64_t ld_qsc,
+                                    const float* q_rnorm, const void* R, int64_t ldr, const void* r_sc,
+                                    int64_t ld_rsc, const float* r_rnorm, float* part, size_t part_bytes,
+                                    void* stream) {
+  AACLIP_REQUIRE(Q && q_sc && q_rnorm && R && r_sc && r_rnorm && part);
+  AACLIP_REQUIRE(M > 0 && Nb > 0 && K > 0 && M <= kBankMaxRows && Nb <= kBankMaxRows && K % 128 == 0);
+  AACLIP_REQUIRE(ldq >= K && ldr >= K && ldq % 16 == 0 && ldr % 16 == 0);
+  AACLIP_REQUIRE(ld_qsc >= M && ld_rsc >= Nb && ld_qsc % 2 == 0 && ld_rsc % 2 == 0);
+  AACLIP_REQUIRE(aligned16(Q) && aligned16(R) && aligned4(q_sc) && aligned4(r_sc));
+  AACLIP_REQUIRE(aligned4(q_rnorm) && aligned4(r_rnorm) && aligned4(part));
+  BankMxArgs x{{Q, R, part, ldq, ldr, M, Nb, K, 0, 0, 0}, (const uint8_t*)q_sc, (const uint8_t*)r_sc, q_rnorm, r_rnorm,
+               ld_qsc, ld_rsc};
+  bank_plan(M, Nb, x.b.tiles_n, x.b.tiles_per_split, x.b.n_splits);
+  AACLIP_REQUIRE(part_bytes >= (size_t)M * x.b.n_splits * sizeof(float));
+  const int64_t blocks = (int64_t)ceil_div(M, BM) * x.b.n_splits;
+  AACLIP_REQUIRE(blocks < (1LL << 31));
+  static unsigned attr_dev = 0;
+  if (!lds_attr_once((const void*)bank_nn_mx_kernel, kLdsMx, attr_dev)) return AACLIP_ERR_LAUNCH;
+  bank_nn_mx_kernel<<<(int)blocks, NWAVES * 64, kLdsMx, (hipStream_t)stream>>>(x);
   AACLIP_CHECK_LAUNCH();
   return AACLIP_OK;
 }

@@ -406,7 +406,78 @@ __global__ __launch_bounds__(256) void quant_mx_kernel(int in_dtype, const void*
   }
 }
 
+// The lane's 4 consecutive elements at p + off elements as fp32, storage read at run time
+__device__ __forceinline__ float4_t load4(const void* p, int dtype, size_t off) {
+  if (dtype == AACLIP_F32) return *(const float4_t*)((const float*)p + off);
+  const uint2 r = *(const uint2*)((const uint16_t*)p + off);
+  if (dtype == AACLIP_F16)
+    return float4_t{f16_to_f32((uint16_t)(r.x & 0xffff)), f16_to_f32((uint16_t)(r.x >> 16)),
+                    f16_to_f32((uint16_t)(r.y & 0xffff)), f16_to_f32((uint16_t)(r.y >> 16))};
+  return float4_t{__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u), __uint_as_float(r.y << 16),
+                  __uint_as_float(r.y & 0xffff0000u)};
+}
+
+// Few-shot search operands in MX fp8 (bank.hip, bank_nn_mx_kernel): a row is L2-normalised as
+// l2norm_kernel does it (the same lane layout and summation order: lane l holds elements
+// 256 c + 4 l .. + 3), MX-quantised by mxfp8.h's rule, and the reciprocal norm of what was
+// STORED (e4m3 * 2^e, squares exact in fp32) goes to rnorm, so the search can return the exact
+// cosine between the fp8 representations. Any width that is a multiple of 128: in a last half
+// chunk lanes 32..63 carry zeros. The row is read twice (the second read hits the cache).
+__global__ __launch_bounds__(256) void unit_rows_mx_kernel(int in_dtype, const void* __restrict__ x, int64_t ldx,
+                                                           uint8_t* __restrict__ q, int64_t ldq,
+                                                           uint8_t* __restrict__ sc, int64_t ld_sc,
+                                                           float* __restrict__ rnorm, int rows, int cols) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const size_t xoff = (size_t)row * ldx;
+  float s = 0.f;
+  for (int c0 = 4 * lane; c0 < cols; c0 += 256) {
+    const float4_t v = load4(x, in_dtype, xoff + c0);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s += v[j] * v[j];
+  }
+  const float inv = 1.0f / fmaxf(sqrtf(wave_sum(s)), 1e-12f);
+  float ss = 0.f;
+  for (int cb = 0; cb < cols; cb += 256) {  // wave-uniform trip count: the shuffles see every lane
+    const int c0 = cb + 4 * lane;
+    const bool live = c0 < cols;
+    float4_t v = float4_t{0.f, 0.f, 0.f, 0.f};
+    if (live) v = load4(x, in_dtype, xoff + c0) * inv;
+    float amax = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+    const int e = mx_exp(amax);
+    const uint32_t w = mx_pack4(v[0], v[1], v[2], v[3], pow2i(-e));
+    const float2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8(w, false), hi = __builtin_amdgcn_cvt_pk_f32_fp8(w, true);
+    const float up = pow2i(e);
+    const float d[4] = {lo[0] * up, lo[1] * up, hi[0] * up, hi[1] * up};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ss += d[j] * d[j];
+    if (live) {
+      *(uint32_t*)(q + (size_t)row * ldq + c0) = w;
+      if ((lane & 15) == 0) *mx_scale_ptr(sc, ld_sc, row, c0 >> 6) = (uint8_t)(e + 127);
+    }
+  }
+  ss = wave_sum(ss);
+  if (lane == 0) rnorm[row] = ss > 0.f ? 1.0f / sqrtf(ss) : 0.f;
+}
+
 }  // namespace
+
+extern "C" int aaclip_unit_rows_fp8mx(int in_dtype, const void* x, int64_t ldx, void* q, int64_t ldq, void* sc,
+                                      int64_t ld_sc, float* rnorm, int rows, int cols, void* stream) {
+  AACLIP_REQUIRE(dtype_ok(in_dtype) && x && q && sc && rnorm && rows >= 0 && cols > 0 && cols % 128 == 0);
+  const int64_t es = in_dtype == AACLIP_F32 ? 4 : 2;
+  AACLIP_REQUIRE(ldx >= cols && ldq >= cols && (ldx * es) % 16 == 0 && ldq % 16 == 0);
+  AACLIP_REQUIRE(ld_sc >= rows && ld_sc % 2 == 0);
+  AACLIP_REQUIRE(aligned16(x) && aligned16(q) && aligned4(sc) && aligned4(rnorm));
+  if (rows == 0) return AACLIP_OK;
+  unit_rows_mx_kernel<<<ceil_div(rows, 4), 256, 0, (hipStream_t)stream>>>(in_dtype, x, ldx, (uint8_t*)q, ldq,
+                                                                          (uint8_t*)sc, ld_sc, rnorm, rows, cols);
+  AACLIP_CHECK_LAUNCH();
+  return AACLIP_OK;
+}
 
 extern "C" int aaclip_embed_ln(int out_dtype, float* x, const float* cls, const float* pos,
                                const float* ln_pre_w, const float* ln_pre_b, const float* ln1_w,

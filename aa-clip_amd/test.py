@@ -28,6 +28,9 @@ Differences from the reference, all on the host side:
     bank of --shot normal support images (get_dataset stage "support"; real datasets list them
     in --support_meta), every test patch scored by its distance to the nearest bank patch at
     every level on the device, and that map fused with the zero-shot one (single process).
+    --few_shot_search fp8 keeps the bank and the test patches in MX fp8 (e4m3, a scale per 64
+    values) and searches on the block-scaled fp8 MFMA, the cosine taken between the stored rows;
+    the default searches in the engine's own search dtype.
 """
 from __future__ import annotations
 
@@ -154,20 +157,21 @@ def get_predictions(model, class_text_embeddings, test_loader, device, img_size,
 
 
 def get_few_shot_predictions(model, class_text_embeddings, test_loader, support_loader, device, img_size,
-                             dataset="MVTec", prep=None, sources=None):
+                             dataset="MVTec", prep=None, sources=None, search="default"):
     """get_predictions for --few_shot (single process): the class's memory bank is built from the
     support loader's normal images (reference test.py:39-50), every test batch goes through
     AdaptedCLIP.predict_few_shot, and the class's zero-shot and few-shot maps and scores are fused
     on the device (aaclip_fewshot_fuse). Returns get_predictions' tuple with the fused maps and
     scores in the place of the zero-shot ones, and a dict of the device tensors behind them:
     zs_map, fs_map, fused_map [N,S,S], zs_score, fs_score, fused_score [N]. The bank is dropped
-    on return. Eager and on one stream; sources as in get_predictions."""
+    on return. Eager and on one stream; sources as in get_predictions. search "fp8": the bank and
+    the search in MX fp8 (--few_shot_search)."""
     from aaclip import ops
     device = torch.device(device)
     support = [_device_batch(batch, prep, device)[0] for batch in support_loader]
     if not support:
         raise ValueError("few-shot scoring needs at least one support image per class")
-    bank = model.build_memory_bank(torch.cat(support))
+    bank = model.build_memory_bank(torch.cat(support), torch.float8_e4m3fn if search == "fp8" else None)
     del support
     masks, labels, zs_maps, zs_scores, fs_maps, file_names = [], [], [], [], [], []
     for input_data in test_loader:
@@ -206,6 +210,10 @@ def parse_args(argv=None):
                         help="few-shot scoring: per class a memory bank of --shot normal support images; every "
                              "test patch's distance to its nearest bank patch, over the levels, is fused with the "
                              "zero-shot map and score (single process)")
+    parser.add_argument("--few_shot_search", type=str, default="default", choices=["default", "fp8"],
+                        help="--few_shot: the nearest-patch search's operands: the engine's own search dtype, or "
+                             "fp8 = bank and test patches in MX fp8 (half the bank's bytes) on the block-scaled "
+                             "fp8 MFMA (ignored without --few_shot)")
     parser.add_argument("--support_meta", type=str, default="",
                         help="--few_shot on a real dataset: jsonl in the metadata line format listing the normal "
                              "support images (the first --shot label-0 lines of each class are used)")
@@ -376,7 +384,7 @@ def run(args):
                     masks, labels, preds, preds_image, file_names, parts = get_few_shot_predictions(
                         model=model, class_text_embeddings=text_embeddings[class_name], test_loader=loader,
                         support_loader=support_loader, device=device, img_size=args.img_size,
-                        dataset=args.dataset, prep=prep, sources=sources)
+                        dataset=args.dataset, prep=prep, sources=sources, search=args.few_shot_search)
                     ctx["few_shot"][class_name] = parts
                 else:
                     masks, labels, preds, preds_image, file_names = get_predictions(

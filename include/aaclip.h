@@ -926,6 +926,42 @@ int aaclip_bank_nn_workspace(int M, int Nb, size_t* bytes, int* n_splits);
 int aaclip_bank_nn(int dtype, int M, int Nb, int K, const void* Q, int64_t ldq, const void* R, int64_t ldr,
                    float* part, size_t part_bytes, void* stream);
 int aaclip_bank_distance(const float* part, int M, int n_splits, int accumulate, float* grid, void* stream);
+
+/*
+ * The same search on MX fp8 operands (csrc/mxfp8.h: e4m3 bytes, one e8m0 scale byte e + 127 per
+ * 64 columns of a row, scale buffer [cols / 128][ld][2]); opt-in, replacing the same reference
+ * lines (test.py:39-50, utils.py:86-93). It returns the exact cosine between the two fp8
+ * representations: quantised unit rows are no longer unit (norms about 1 +- 6e-3), so each side
+ * carries the reciprocal norm of what it stored.
+ *
+ * aaclip_unit_rows_fp8mx: per row of x [rows, cols] (`in_dtype` AACLIP_F32 / _BF16 / _F16, row
+ * stride ldx elements): y = x / max(|x|, 1e-12), |x| summed as aaclip_l2_normalize sums it; q =
+ * y in MX e4m3 (RNE) with row stride ldq bytes, scales into sc [cols / 128][ld_sc][2], ld_sc >=
+ * rows and even; rnorm[r] = 1 / sqrt(sum_c deq[r, c]^2) in fp32, deq = e4m3 * 2^e the values the
+ * search reads (the squares are exact, the root and the reciprocal correctly rounded, so a
+ * power-of-two norm gives that power of two), and 0 for a row that stores all zeros. cols is any
+ * multiple of 128; x and q 16-byte aligned with 16-byte aligned row strides >= cols, sc and rnorm
+ * 4-byte aligned. rows == 0 is a no-op.
+ *
+ * aaclip_bank_nn_fp8mx: part[m][s] = max over the bank rows n of split s of
+ * (Q^[m] . R^[n]) * r_rnorm[n] * q_rnorm[m], Q^ / R^ the dequantised rows; the dot product on
+ * v_mfma_scale_f32_16x16x128_f8f6f4 with both block scales applied by the instruction, fp32
+ * accumulation over K-steps of 128 ascending. Q [M, K], R [Nb, K] e4m3 bytes (strides in bytes),
+ * q_sc / r_sc their scale buffers with row counts ld_qsc >= M, ld_rsc >= Nb, both even; q_rnorm
+ * [M], r_rnorm [Nb] fp32 (aaclip_unit_rows_fp8mx writes all three). K % 128 == 0. The tiles, the
+ * split plan (aaclip_bank_nn_workspace), `part`, the clamped ragged edges and the same-bits
+ * properties are aaclip_bank_nn's; part holds cosines, so aaclip_bank_distance takes it as it
+ * is. A bank row with r_rnorm 0 scores 0. Scales must not be 255 (NaN); values finite.
+ * Q and R 16-byte aligned, the rest 4-byte; row strides multiples of 16.
+ *
+ * Both return AACLIP_ERR_ARG before any launch for NULL pointers, M or Nb < 1, a width that is
+ * no multiple of 128, an odd or short ld_sc, short or misaligned strides or a short `part`.
+ */
+int aaclip_unit_rows_fp8mx(int in_dtype, const void* x, int64_t ldx, void* q, int64_t ldq, void* sc, int64_t ld_sc,
+                           float* rnorm, int rows, int cols, void* stream);
+int aaclip_bank_nn_fp8mx(int M, int Nb, int K, const void* Q, int64_t ldq, const void* q_sc, int64_t ld_qsc,
+                         const float* q_rnorm, const void* R, int64_t ldr, const void* r_sc, int64_t ld_rsc,
+                         const float* r_rnorm, float* part, size_t part_bytes, void* stream);
 int aaclip_fewshot_fuse(const float* zs_map, const float* fs_map, const float* zs_score, int n_images,
                         int64_t pix_per_image, void* workspace, size_t workspace_bytes, float* fused_map,
                         float* fs_score, float* fused_score, void* stream);
