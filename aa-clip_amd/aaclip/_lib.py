@@ -118,6 +118,8 @@ SIGNATURES = {
     "aaclip_unit_rows_fp8mx": [_I, _P, _L, _P, _L, _P, _L, _P, _I, _I, _P],
     "aaclip_bank_nn_fp8mx": [_I, _I, _I, _P, _L, _P, _L, _P, _P, _L, _P, _L, _P, _P, ctypes.c_size_t, _P],
     "aaclip_fewshot_fuse": [_P, _P, _P, _I, _L, _P, ctypes.c_size_t, _P, _P, _P, _P],
+    "aaclip_bank_coreset_workspace": [_I, ctypes.POINTER(ctypes.c_size_t)],
+    "aaclip_bank_coreset": [_I, _I, _I, _P, _L, _I, _I, _P, _P, _P, _P, ctypes.c_size_t, _P],
 }
 
 _lib = None

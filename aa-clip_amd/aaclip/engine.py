@@ -256,15 +256,27 @@ def _block_bwd(g, blk: dict, bt: dict, sv: dict, attend_bwd, act_mode: str, d_qk
 
 class MemoryBank:
     """The few-shot memory bank of one class (VisualEngine.build_bank): levels, a list of L device
-    tensors [shots * P, 768] of unit patch rows (dtype float8_e4m3fn: of ops.Fp8MxRows, the rows in
+    tensors [rows, 768] of unit patch rows (dtype float8_e4m3fn: of ops.Fp8MxRows, the rows in
     MX fp8 with their block scales and reciprocal norms); img_size and dtype, which a
-    predict_few_shot call must match; shots, the number of support images."""
+    predict_few_shot call must match; shots, the number of support images. source_rows: the
+    shots * P rows per level the bank was built from. A coreset bank (build_bank(coreset=ratio))
+    keeps ops.coreset_rows(source_rows, ratio) of them per level, in pick order, and carries per
+    level coreset_index (int32 [rows], the kept source rows), cover (fp32 [rows], each pick's
+    similarity to the picks before it) and coverage (0-d fp32, the smallest cosine between any
+    source row and its nearest kept row); all three are None for a full bank."""
 
-    def __init__(self, levels: list, img_size: int, dtype: torch.dtype, shots: int):
+    def __init__(self, levels: list, img_size: int, dtype: torch.dtype, shots: int, *, source_rows=None,
+                 coreset_index=None, cover=None, coverage=None):
         self.levels, self.img_size, self.dtype, self.shots = list(levels), int(img_size), dtype, int(shots)
+        self.source_rows = int(source_rows) if source_rows is not None else self.rows
+        self.coreset_index, self.cover, self.coverage = coreset_index, cover, coverage
+
+    @property
+    def rows(self):
+        return self.levels[0].shape[0] if self.levels else 0
 
     def __repr__(self):
-        return (f"MemoryBank(levels={len(self.levels)}, rows={self.levels[0].shape[0] if self.levels else 0}, "
+        return (f"MemoryBank(levels={len(self.levels)}, rows={self.rows}/{self.source_rows}, "
                 f"img_size={self.img_size}, dtype={self.dtype}, shots={self.shots})")
 
 
@@ -871,22 +883,59 @@ class VisualEngine:
         parts = [[s_.clone() for s_ in self.forward_raw(x[b0:min(B, b0 + mc)])[0]] for b0 in range(0, B, mc)]
         return [ops.unit_rows_fp8mx(torch.cat(lv)) for lv in zip(*parts)]
 
-    def build_bank(self, support_images: torch.Tensor, search_dtype=None) -> "MemoryBank":
+    def build_bank(self, support_images: torch.Tensor, search_dtype=None, coreset=None) -> "MemoryBank":
         """The memory bank of k normal support images [k, 3, S, S] (reference test.py:39-50,
         get_support_features): per level the k*P unit patch rows, in search_dtype. search_dtype
         torch.float8_e4m3fn (any engine mode) keeps them in MX fp8 instead, half the bytes, for the
-        block-scaled fp8 search; None is the engine's own."""
+        block-scaled fp8 search; None is the engine's own. coreset: None or 1.0 keeps every row; a
+        ratio in (0, 1) keeps per level the greedy k-centre coreset of ops.coreset_rows(k*P, ratio)
+        rows (ops.bank_coreset from row 0, on the unit rows in this engine's search_dtype whatever
+        the bank's dtype), in pick order."""
         _check_image(support_images)
         if support_images.shape[0] < 1:
             raise ValueError("build_bank needs at least one support image")
         if search_dtype is not None and search_dtype not in (self.search_dtype, torch.float8_e4m3fn):
             raise ValueError(f"build_bank: search_dtype must be None, {self.search_dtype} (this engine's) or "
                              f"torch.float8_e4m3fn, got {search_dtype}")
+        if coreset is not None and not 0.0 < float(coreset) <= 1.0:
+            raise ValueError(f"build_bank: coreset must be None or a ratio in (0, 1], got {coreset}")
+        if coreset is not None and float(coreset) != 1.0:
+            return self._build_coreset_bank(support_images, search_dtype == torch.float8_e4m3fn, float(coreset))
         if search_dtype == torch.float8_e4m3fn:
             return MemoryBank(self.bank_rows_fp8mx(support_images), int(support_images.shape[-1]),
                               torch.float8_e4m3fn, int(support_images.shape[0]))
         return MemoryBank(self.bank_rows(support_images), int(support_images.shape[-1]), self.search_dtype,
                           int(support_images.shape[0]))
+
+    @torch.no_grad()
+    @_on_device
+    def _build_coreset_bank(self, x: torch.Tensor, fp8: bool, ratio: float) -> "MemoryBank":
+        """build_bank with a coreset: the selection runs per level on the search_dtype unit rows; an
+        fp8 bank then quantises only the selected raw rows (so its rows are the ones a full fp8
+        bank holds at those indices)."""
+        B, S = x.shape[0], x.shape[-1]
+        if fp8:  # the raw rows outlive the next forward_raw only as copies
+            mc = self.max_chunk(S)
+            if B <= mc:
+                raw = list(self.forward_raw(x)[0])
+            else:
+                parts = [[s_.clone() for s_ in self.forward_raw(x[b0:min(B, b0 + mc)])[0]] for b0 in range(0, B, mc)]
+                raw = [torch.cat(lv) for lv in zip(*parts)]
+            unit = self._unit_rows(raw)
+        else:
+            unit = self.bank_rows(x)
+        n = int(unit[0].shape[0])
+        m = ops.coreset_rows(n, ratio)
+        levels, index, cover, coverage = [], [], [], []
+        for j, u in enumerate(unit):
+            sel, cov, maxsim = ops.bank_coreset(u, m, 0)
+            at = sel.long()
+            levels.append(ops.unit_rows_fp8mx(raw[j].index_select(0, at)) if fp8 else u.index_select(0, at))
+            index.append(sel)
+            cover.append(cov)
+            coverage.append(maxsim.min())
+        return MemoryBank(levels, int(S), torch.float8_e4m3fn if fp8 else self.search_dtype, int(B), source_rows=n,
+                          coreset_index=index, cover=cover, coverage=coverage)
 
     @torch.no_grad()
     @_on_device

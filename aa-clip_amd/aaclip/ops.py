@@ -8,6 +8,7 @@ HIP kernel on torch's current stream. There is no eager-PyTorch fallback.
 from __future__ import annotations
 
 import ctypes
+import math
 
 import torch
 
@@ -1692,6 +1693,59 @@ def bank_distance(part, grid, *, accumulate: bool):
     _launch("fewshot", "bank_distance", 0.0, 4.0 * part.numel() + 8.0 * M, "aaclip_bank_distance", _ptr(part), M,
             n_splits, int(bool(accumulate)), _ptr(grid), _stream())
     return grid
+
+
+CORESET_MAX_K = 4096        # AACLIP_CORESET_MAX_K
+CORESET_BLOCK_ROWS = 64     # AACLIP_CORESET_BLOCK_ROWS: rows per slab
+CORESET_MAX_BLOCKS = 512    # AACLIP_CORESET_MAX_BLOCKS: candidates per step
+
+
+def coreset_rows(n: int, ratio: float) -> int:
+    """Rows a coreset of `ratio` keeps of n: max(1, ceil(ratio * n)), for 0 < ratio <= 1."""
+    if not 0.0 < float(ratio) <= 1.0:
+        raise ValueError(f"a coreset ratio must lie in (0, 1], got {ratio}")
+    if int(n) < 1:
+        raise ValueError(f"a coreset needs at least one row, got {n}")
+    return min(int(n), max(1, math.ceil(float(ratio) * int(n))))
+
+
+def coreset_blocks(n: int) -> int:
+    """Blocks (= candidates per step) of a bank_coreset launch on n rows: the slabs dealt evenly
+    over the fewest grid-stride trips that stay within CORESET_MAX_BLOCKS (csrc/bank.hip)."""
+    slabs = -(-int(n) // CORESET_BLOCK_ROWS)
+    return -(-slabs // -(-slabs // CORESET_MAX_BLOCKS))
+
+
+def bank_coreset(rows, m: int, start: int = 0):
+    """Greedy k-centre coreset of rows [N, K] (aaclip_bank_coreset; tests/coreset_ref.py): from
+    `start`, m - 1 times the row whose largest dot product with the rows picked so far is smallest,
+    the lowest index on ties -- farthest-point selection under 1 - cosine when the rows are unit
+    (normalising them is the caller's job). rows: float16, bfloat16 or float32, unit column stride,
+    any 16-byte aligned row stride, K a multiple of 64 up to CORESET_MAX_K, finite values.
+    Returns (sel int32 [m] in pick order, cover fp32 [m]: each pick's similarity to the picks
+    before it (cover[0] = -inf), maxsim fp32 [N]: every row's largest similarity to a picked row).
+    m launches on the current stream, no host sync."""
+    _bank_rows(rows, "rows")
+    tag = dtag(rows)
+    N, K = rows.shape
+    m, start = int(m), int(start)
+    if K % 64 or K == 0 or K > CORESET_MAX_K:
+        raise ValueError(f"bank_coreset needs rows [N, K] with K a multiple of 64 up to {CORESET_MAX_K}, got "
+                         f"{tuple(rows.shape)}")
+    if N > 1 << 30 or not 1 <= m <= N or not 0 <= start < N:
+        raise ValueError(f"bank_coreset needs 1 <= m <= N <= 2^30 and 0 <= start < N, got m = {m}, start = {start}, "
+                         f"N = {N}")
+    _dev(rows)
+    need = ctypes.c_size_t(0)
+    call("aaclip_bank_coreset_workspace", N, ctypes.byref(need))
+    ws, at = _aligned_workspace(int(need.value), rows.device)
+    sel = torch.empty(m, device=rows.device, dtype=torch.int32)
+    cover = torch.empty(m, device=rows.device, dtype=torch.float32)
+    maxsim = torch.empty(N, device=rows.device, dtype=torch.float32)
+    _launch("fewshot", "bank_coreset", 2.0 * m * N * K, float(m) * N * K * rows.element_size(),
+            "aaclip_bank_coreset", tag, N, K, _ptr(rows), rows.stride(0), m, start, _ptr(sel), _ptr(cover),
+            _ptr(maxsim), at, int(need.value), _stream())
+    return sel, cover, maxsim
 
 
 def fewshot_fuse(zs_map, fs_map, zs_score):

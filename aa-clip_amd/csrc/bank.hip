@@ -32,9 +32,12 @@
 //   combine   aaclip_bank_distance: grid[m] = (accumulate ? grid[m] : 0) + (1 - max_s part[m][s]).
 //   fusion    aaclip_fewshot_fuse: class-normalised zero-shot + few-shot maps and scores, every
 //             operation a rounded fp32 one (tests/fewshot_ref.py states it in numpy float32).
+//   coreset   aaclip_bank_coreset: greedy k-centre subsampling of a bank ahead of the search, one
+//             step kernel per pick (coreset_step_kernel; tests/coreset_ref.py states it in float64).
 //
 // Inputs are finite: the object is built with -fno-honor-nans (Makefile), which drops the
 // canonicalising v_max hipcc otherwise puts in front of every fmaxf of an MFMA result.
+#include <climits>
 #include <cmath>
 
 #include "common.h"
@@ -456,6 +459,171 @@ __global__ __launch_bounds__(MT) void fewshot_fuse_kernel(const float* __restric
     fused_score[i0] = unit_range(zs_score[i0], ranges[4], ranges[5]) + unit_range(fs_score[i0], ranges[6], ranges[7]);
 }
 
+// ============================================================== greedy k-centre coreset
+// aaclip_bank_coreset: farthest-point selection under 1 - cosine on unit rows (PatchCore's coreset
+// subsampling), one launch of coreset_step_kernel per pick: the step boundary is the launch
+// boundary, so there is no grid-wide wait, no atomic and no spin on memory.
+//   centre    every block reduces the previous step's per-block candidates (value, index) to their
+//             lexicographic minimum -- the same set in every block, and a minimum under a total
+//             order does not depend on the reduction tree -- and block 0 stores sel[t], cover[t].
+//   pass      the centre row goes to LDS as fp32; a block walks its slabs of CS_ROWS rows (slab
+//             b, b + grid, ...: a function of N alone, the same in every step, so a row's bytes
+//             keep coming from the same XCD's L2 and the Infinity Cache). Sixteen lanes share a
+//             row, lane l taking its 16-byte chunks l, l + 16, ...; a wave has four such groups and
+//             four passes of them in flight, so a lane holds four independent 16-byte loads per
+//             chunk column against one LDS read of the centre.
+//   order     a dot product is: per lane one fp32 accumulator from +0, fmaf over the lane's chunks
+//             ascending and the elements of a chunk ascending; then across the sixteen lanes the
+//             butterfly a += shfl_xor(a, 8), 4, 2, 1. A function of K and the dtype alone.
+//   update    the group's lane 0 owns the row: maxsim = max(maxsim, dot) (step 0: = dot), the taken
+//             byte (step 0 writes every row's, later steps only the centre's), and the running
+//             (value, index) minimum over its rows that are not taken; wave shuffle and LDS bring
+//             the block's candidate to thread 0, which stores it into the buffer of t's parity.
+constexpr int CS_ROWS = AACLIP_CORESET_BLOCK_ROWS, CS_THREADS = 256, CS_WAVES = CS_THREADS / 64;
+constexpr int CS_GROUP = 16, CS_PASSES = CS_ROWS / (CS_WAVES * (64 / CS_GROUP));
+static_assert(CS_PASSES * CS_WAVES * (64 / CS_GROUP) == CS_ROWS, "a slab is whole passes of every wave");
+typedef __attribute__((ext_vector_type(2))) int int2_t;
+constexpr size_t kCoresetCandBytes = 2 * (size_t)AACLIP_CORESET_MAX_BLOCKS * sizeof(int2_t);
+
+struct CoresetArgs {
+  const void* R;
+  int64_t ldr;  // elements
+  int N, K, t, start;
+  int32_t* sel;
+  float* cover;
+  float* maxsim;
+  int2_t* cand;    // [2][AACLIP_CORESET_MAX_BLOCKS] (value bits, index)
+  uint8_t* taken;  // [N]
+};
+
+// (v, i) < (bv, bi) in the order the pick minimises: the value, then the index
+__device__ __forceinline__ void cand_min(float& bv, int& bi, float v, int i) {
+  if (v < bv || (v == bv && i < bi)) bv = v, bi = i;
+}
+
+// the block's minimum of (v, i), in every thread; red: 2 * CS_WAVES words nobody else uses now
+__device__ __forceinline__ void cand_block_min(float& v, int& i, float* red_v, int* red_i) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cand_min(v, i, __shfl_xor(v, o, 64), __shfl_xor(i, o, 64));
+  if ((threadIdx.x & 63) == 0) red_v[threadIdx.x >> 6] = v, red_i[threadIdx.x >> 6] = i;
+  __syncthreads();
+  v = red_v[0], i = red_i[0];
+#pragma unroll
+  for (int w = 1; w < CS_WAVES; ++w) cand_min(v, i, red_v[w], red_i[w]);
+}
+
+// DT: AACLIP_F32 (4 elements per 16-byte chunk), AACLIP_BF16 / AACLIP_F16 (8)
+template <int DT>
+__global__ __launch_bounds__(CS_THREADS) void coreset_step_kernel(CoresetArgs a) {
+  constexpr int ES = DT == AACLIP_F32 ? 4 : 2, EPC = 16 / ES;
+  __shared__ __attribute__((aligned(16))) float cs[AACLIP_CORESET_MAX_K];
+  __shared__ float red_v[2][CS_WAVES];
+  __shared__ int red_i[2][CS_WAVES];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int nblocks = gridDim.x, nchunks = a.K / EPC;
+
+  // ---- the centre
+  int centre = a.start;
+  float cov = -INFINITY;
+  if (a.t > 0) {
+    const int2_t* prev = a.cand + (size_t)((a.t - 1) & 1) * AACLIP_CORESET_MAX_BLOCKS;
+    cov = INFINITY, centre = INT_MAX;
+    for (int j = tid; j < nblocks; j += CS_THREADS) {
+      const int2_t c = prev[j];
+      cand_min(cov, centre, __int_as_float(c[0]), c[1]);
+    }
+    cand_block_min(cov, centre, red_v[0], red_i[0]);
+    // t < N, so some row was not taken and the minimum is a row; non-finite inputs (outside the
+    // contract) could leave INT_MAX here, and the centre is an address
+    centre = min(centre, a.N - 1);
+  }
+  if (blockIdx.x == 0 && tid == 0) a.sel[a.t] = centre, a.cover[a.t] = cov;
+
+  // ---- the centre row into LDS, fp32
+  const char* Rg = (const char*)a.R;
+  const size_t row_bytes = (size_t)a.ldr * ES;
+  auto widen = [](const float4_t raw, float (&f)[EPC]) {
+    if constexpr (DT == AACLIP_F32) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) f[e] = raw[e];
+    } else {
+      const short8_t h = __builtin_bit_cast(short8_t, raw);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) f[e] = h16_to_f32<DT == AACLIP_F16>((uint16_t)h[e]);
+    }
+  };
+  for (int c = tid; c < nchunks; c += CS_THREADS) {
+    float f[EPC];
+    widen(*(const float4_t*)(Rg + (size_t)centre * row_bytes + (size_t)c * 16), f);
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) cs[c * EPC + e] = f[e];
+  }
+  __syncthreads();
+
+  // ---- the block's rows
+  const int g = lane >> 4, l = lane & 15;
+  const int slabs = ceil_div(a.N, CS_ROWS);
+  float best_v = INFINITY;
+  int best_i = INT_MAX;
+  for (int slab = blockIdx.x; slab < slabs; slab += nblocks) {
+    const int row0 = slab * CS_ROWS + wid * (CS_ROWS / CS_WAVES) + g;  // pass p: row0 + 4 p
+    const char* src[CS_PASSES];
+    float acc[CS_PASSES];
+#pragma unroll
+    for (int p = 0; p < CS_PASSES; ++p) {
+      src[p] = Rg + (size_t)min(row0 + 4 * p, a.N - 1) * row_bytes;  // past the end: the last row, not stored
+      acc[p] = 0.f;
+    }
+#pragma unroll 2
+    for (int c = l; c < nchunks; c += CS_GROUP) {
+      float4_t raw[CS_PASSES];
+#pragma unroll
+      for (int p = 0; p < CS_PASSES; ++p) raw[p] = *(const float4_t*)(src[p] + (size_t)c * 16);
+      float cf[EPC];
+#pragma unroll
+      for (int e = 0; e < EPC; e += 4) {
+        const float4_t v = *(const float4_t*)(cs + c * EPC + e);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cf[e + j] = v[j];
+      }
+#pragma unroll
+      for (int p = 0; p < CS_PASSES; ++p) {
+        float rf[EPC];
+        widen(raw[p], rf);
+#pragma unroll
+        for (int e = 0; e < EPC; ++e) acc[p] = fmaf(rf[e], cf[e], acc[p]);
+      }
+    }
+#pragma unroll
+    for (int p = 0; p < CS_PASSES; ++p) {
+      float d = acc[p];
+#pragma unroll
+      for (int o = CS_GROUP / 2; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+      const int row = row0 + 4 * p;
+      if (l == 0 && row < a.N) {
+        const float ms = a.t == 0 ? d : fmaxf(a.maxsim[row], d);
+        a.maxsim[row] = ms;
+        bool tk = row == centre;
+        if (a.t == 0 || tk)
+          a.taken[row] = tk;
+        else
+          tk = a.taken[row] != 0;
+        if (!tk) cand_min(best_v, best_i, ms, row);
+      }
+    }
+  }
+  cand_block_min(best_v, best_i, red_v[1], red_i[1]);
+  if (tid == 0)
+    a.cand[(size_t)(a.t & 1) * AACLIP_CORESET_MAX_BLOCKS + blockIdx.x] = int2_t{__float_as_int(best_v), best_i};
+}
+
+// blocks of a coreset launch: the slabs dealt evenly over the fewest grid-stride trips that keep
+// the block count within AACLIP_CORESET_MAX_BLOCKS. A function of N alone.
+int coreset_blocks(int N) {
+  const int slabs = ceil_div(N, CS_ROWS);
+  return ceil_div(slabs, ceil_div(slabs, AACLIP_CORESET_MAX_BLOCKS));
+}
+
 // the split of the bank tiles over blocks: of the even splits into at most AACLIP_BANK_MAX_SPLITS
 // parts (never an empty one) the one whose blocks take the fewest rounds x tiles on a chip that
 // holds AACLIP_BANK_RESIDENT_BLOCKS of them at once (one per CU: 128 KiB of LDS each), a block
@@ -575,5 +743,38 @@ extern "C" int aaclip_fewshot_fuse(const float* zs_map, const float* fs_map, con
   fewshot_fuse_kernel<<<(int)blocks, MT, 0, s>>>(zs_map, fs_map, zs_score, fs_score, ranges, total, n_images,
                                                 fused_map, fused_score);
   AACLIP_CHECK_LAUNCH();
+  return AACLIP_OK;
+}
+
+extern "C" int aaclip_bank_coreset_workspace(int N, size_t* bytes) {
+  AACLIP_REQUIRE(bytes && N > 0 && N <= kBankMaxRows);
+  *bytes = kCoresetCandBytes + (((size_t)N + 15) & ~(size_t)15);  // the candidates, then the taken bytes
+  return AACLIP_OK;
+}
+
+extern "C" int aaclip_bank_coreset(int dtype, int N, int K, const void* R, int64_t ldr, int m, int start,
+                                   int32_t* sel, float* cover, float* maxsim, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  AACLIP_REQUIRE(R && sel && cover && maxsim && workspace && N > 0 && N <= kBankMaxRows && K > 0);
+  AACLIP_REQUIRE(dtype == AACLIP_F32 || dtype == AACLIP_BF16 || dtype == AACLIP_F16);
+  const int64_t es = dtype == AACLIP_F32 ? 4 : 2;
+  AACLIP_REQUIRE(K % 64 == 0 && K <= AACLIP_CORESET_MAX_K && ldr >= K && (ldr * es) % 16 == 0);
+  AACLIP_REQUIRE(m >= 1 && m <= N && start >= 0 && start < N);
+  AACLIP_REQUIRE(aligned16(R) && aligned16(workspace) && aligned4(sel) && aligned4(cover) && aligned4(maxsim));
+  size_t need = 0;
+  AACLIP_REQUIRE(aaclip_bank_coreset_workspace(N, &need) == AACLIP_OK && workspace_bytes >= need);
+  CoresetArgs a{R, ldr, N, K, 0, start, sel, cover, maxsim, (int2_t*)workspace,
+                (uint8_t*)workspace + kCoresetCandBytes};
+  const int blocks = coreset_blocks(N);
+  hipStream_t s = (hipStream_t)stream;
+  for (a.t = 0; a.t < m; ++a.t) {
+    if (dtype == AACLIP_F32)
+      coreset_step_kernel<AACLIP_F32><<<blocks, CS_THREADS, 0, s>>>(a);
+    else if (dtype == AACLIP_F16)
+      coreset_step_kernel<AACLIP_F16><<<blocks, CS_THREADS, 0, s>>>(a);
+    else
+      coreset_step_kernel<AACLIP_BF16><<<blocks, CS_THREADS, 0, s>>>(a);
+    AACLIP_CHECK_LAUNCH();
+  }
   return AACLIP_OK;
 }

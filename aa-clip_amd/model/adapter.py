@@ -157,11 +157,12 @@ class AdaptedCLIP(nn.Module):
         The outputs are engine-owned buffers: clone them to keep them (test.py does)."""
         return self.visual_engine().predict_cached(x, text_features, domain, streams=streams)
 
-    def build_memory_bank(self, images, search_dtype=None):
+    def build_memory_bank(self, images, search_dtype=None, coreset=None):
         """The few-shot memory bank of a class from its normal support images [k, 3, S, S]
         (reference test.py:39-50, get_support_features): VisualEngine.build_bank. search_dtype
-        torch.float8_e4m3fn keeps the bank in MX fp8 for the block-scaled fp8 search."""
-        return self.visual_engine().build_bank(images, search_dtype)
+        torch.float8_e4m3fn keeps the bank in MX fp8 for the block-scaled fp8 search; coreset, a
+        ratio in (0, 1), keeps per level only that share of the rows, a greedy k-centre coreset."""
+        return self.visual_engine().build_bank(images, search_dtype, coreset)
 
     def predict_few_shot(self, x, text_features, bank, domain="Industrial"):
         """(zero-shot map [B,S,S], zero-shot score [B], few-shot map [B,S,S]), fp32, fresh tensors:

@@ -30,7 +30,9 @@ Differences from the reference, all on the host side:
     every level on the device, and that map fused with the zero-shot one (single process).
     --few_shot_search fp8 keeps the bank and the test patches in MX fp8 (e4m3, a scale per 64
     values) and searches on the block-scaled fp8 MFMA, the cosine taken between the stored rows;
-    the default searches in the engine's own search dtype.
+    the default searches in the engine's own search dtype. --bank_coreset RATIO keeps per level
+    only that share of the bank's rows, a greedy k-centre coreset selected on the device (the
+    subsampling of the PatchCore family of memory-bank detectors; the reference has none).
 """
 from __future__ import annotations
 
@@ -157,7 +159,7 @@ def get_predictions(model, class_text_embeddings, test_loader, device, img_size,
 
 
 def get_few_shot_predictions(model, class_text_embeddings, test_loader, support_loader, device, img_size,
-                             dataset="MVTec", prep=None, sources=None, search="default"):
+                             dataset="MVTec", prep=None, sources=None, search="default", coreset=1.0):
     """get_predictions for --few_shot (single process): the class's memory bank is built from the
     support loader's normal images (reference test.py:39-50), every test batch goes through
     AdaptedCLIP.predict_few_shot, and the class's zero-shot and few-shot maps and scores are fused
@@ -165,13 +167,19 @@ def get_few_shot_predictions(model, class_text_embeddings, test_loader, support_
     scores in the place of the zero-shot ones, and a dict of the device tensors behind them:
     zs_map, fs_map, fused_map [N,S,S], zs_score, fs_score, fused_score [N]. The bank is dropped
     on return. Eager and on one stream; sources as in get_predictions. search "fp8": the bank and
-    the search in MX fp8 (--few_shot_search)."""
+    the search in MX fp8 (--few_shot_search). coreset: the share of the bank's rows kept per level,
+    a greedy k-centre coreset (--bank_coreset; 1.0 keeps all). The dict also carries "bank":
+    {"rows", "source_rows": kept and source rows per level, "coverage": per level the smallest
+    cosine between a source row and its nearest kept row, None for a full bank}."""
     from aaclip import ops
     device = torch.device(device)
     support = [_device_batch(batch, prep, device)[0] for batch in support_loader]
     if not support:
         raise ValueError("few-shot scoring needs at least one support image per class")
-    bank = model.build_memory_bank(torch.cat(support), torch.float8_e4m3fn if search == "fp8" else None)
+    bank = model.build_memory_bank(torch.cat(support), torch.float8_e4m3fn if search == "fp8" else None,
+                                   None if coreset == 1.0 else coreset)
+    bank_info = {"rows": bank.rows, "source_rows": bank.source_rows,
+                 "coverage": None if bank.coverage is None else [float(c) for c in bank.coverage]}
     del support
     masks, labels, zs_maps, zs_scores, fs_maps, file_names = [], [], [], [], [], []
     for input_data in test_loader:
@@ -194,8 +202,15 @@ def get_few_shot_predictions(model, class_text_embeddings, test_loader, support_
     zs_map, zs_score, fs_map = torch.cat(zs_maps), torch.cat(zs_scores), torch.cat(fs_maps)
     fused_map, fs_score, fused_score = ops.fewshot_fuse(zs_map, fs_map, zs_score)
     parts = {"zs_map": zs_map, "fs_map": fs_map, "fused_map": fused_map, "zs_score": zs_score,
-             "fs_score": fs_score, "fused_score": fused_score}
+             "fs_score": fs_score, "fused_score": fused_score, "bank": bank_info}
     return masks, labels, fused_map, fused_score, file_names, parts
+
+
+def _coreset_ratio(text):
+    value = float(text)
+    if not 0.0 < value <= 1.0:
+        raise argparse.ArgumentTypeError(f"a coreset ratio lies in (0, 1], got {text}")
+    return value
 
 
 def parse_args(argv=None):
@@ -214,6 +229,10 @@ def parse_args(argv=None):
                         help="--few_shot: the nearest-patch search's operands: the engine's own search dtype, or "
                              "fp8 = bank and test patches in MX fp8 (half the bank's bytes) on the block-scaled "
                              "fp8 MFMA (ignored without --few_shot)")
+    parser.add_argument("--bank_coreset", type=_coreset_ratio, default=1.0, metavar="RATIO",
+                        help="--few_shot: keep only this share of the memory bank's rows per level, a greedy "
+                             "k-centre coreset selected on the device; in (0, 1], 1.0 keeps every row (ignored "
+                             "without --few_shot)")
     parser.add_argument("--support_meta", type=str, default="",
                         help="--few_shot on a real dataset: jsonl in the metadata line format listing the normal "
                              "support images (the first --shot label-0 lines of each class are used)")
@@ -272,7 +291,8 @@ def run(args):
     recall, with --regions also "regions": per class {"threshold", "images": [{"file_name",
     "n_regions", "regions"}]}, see forward_utils.anomaly_regions, with --few_shot also
     "few_shot": per class the device tensors zs_map, fs_map, fused_map, zs_score, fs_score,
-    fused_score; the class's preds and preds_image are then the fused ones) for callers/tests."""
+    fused_score and "bank", the kept / source rows and the coreset's coverage per level; the
+    class's preds and preds_image are then the fused ones) for callers/tests."""
     setup_seed(args.seed)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -384,8 +404,13 @@ def run(args):
                     masks, labels, preds, preds_image, file_names, parts = get_few_shot_predictions(
                         model=model, class_text_embeddings=text_embeddings[class_name], test_loader=loader,
                         support_loader=support_loader, device=device, img_size=args.img_size,
-                        dataset=args.dataset, prep=prep, sources=sources, search=args.few_shot_search)
+                        dataset=args.dataset, prep=prep, sources=sources, search=args.few_shot_search,
+                        coreset=args.bank_coreset)
                     ctx["few_shot"][class_name] = parts
+                    info = parts["bank"]
+                    logger.info("%s few-shot bank: %d of %d rows per level%s", class_name, info["rows"],
+                                info["source_rows"], "" if info["coverage"] is None else
+                                ", coverage " + ", ".join("%.4f" % c for c in info["coverage"]))
                 else:
                     masks, labels, preds, preds_image, file_names = get_predictions(
                         model=model, class_text_embeddings=text_embeddings[class_name], test_loader=loader,

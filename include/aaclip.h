@@ -967,6 +967,60 @@ int aaclip_fewshot_fuse(const float* zs_map, const float* fs_map, const float* z
                         float* fs_score, float* fused_score, void* stream);
 
 /*
+ * Greedy k-centre coreset of a memory bank (csrc/bank.hip): the subsampling that memory-bank
+ * detectors of the PatchCore family apply to their bank; the reference has nothing of the kind.
+ * Farthest-point selection under the distance 1 - cosine on rows taken as given (normalising
+ * them is the caller's job, as for aaclip_bank_nn); tests/coreset_ref.py states it in float64:
+ *
+ *   maxsim = -inf everywhere; sel[0] = start; cover[0] = -inf
+ *   for t in 0 .. m-1:
+ *     c = sel[t]; c is taken
+ *     maxsim[n] = max(maxsim[n], R[n,:] . R[c,:])        every row, taken ones included
+ *     if t < m-1: sel[t+1] = the lowest index attaining the minimum of maxsim over the rows not
+ *                 taken; cover[t+1] = that minimum
+ *
+ * aaclip_bank_coreset: R [N, K] of `dtype` AACLIP_F16, AACLIP_BF16 or AACLIP_F32 with row stride
+ * ldr in elements; K % 64 == 0 and K <= AACLIP_CORESET_MAX_K (the centre row is staged in LDS as
+ * fp32); R 16-byte aligned with a 16-byte aligned row stride >= K; 1 <= m <= N <= 2^30,
+ * 0 <= start < N. Outputs: sel int32 [m], cover fp32 [m], maxsim fp32 [N] (after the last pick;
+ * its minimum is the smallest cosine between any row and its nearest selected row), 4-byte
+ * aligned. workspace: 16-byte aligned caller-owned device memory of aaclip_bank_coreset_workspace(N)
+ * bytes (host only): two buffers of AACLIP_CORESET_MAX_BLOCKS (value, index) candidates, then a
+ * taken byte per row; it needs no initialisation. Inputs must be finite.
+ *
+ * The call enqueues m launches of one step kernel on `stream`, nothing else: no host
+ * synchronisation, no allocation, no atomics, no cooperative launch, no grid-wide wait. Step t:
+ * every block reduces step t-1's per-block candidates to the (value, index) minimum, the lowest
+ * index on ties (redundantly: blocks^2 x 8 bytes of L2 reads per step, which is what
+ * AACLIP_CORESET_MAX_BLOCKS caps), block 0 stores sel[t] and cover[t]; the block stages the centre
+ * row in LDS, streams its own rows once with 16-byte loads, updates maxsim, marks the centre as
+ * taken and writes its own candidate into the buffer of t's parity (step t-1's is still being read
+ * by other blocks). The rows are cut into slabs of AACLIP_CORESET_BLOCK_ROWS; the launch has
+ * ceil(slabs / ceil(slabs / AACLIP_CORESET_MAX_BLOCKS)) blocks and block b owns slabs b, b + blocks,
+ * ...: a function of N alone and the same in every step, so a row has one owner (no race on
+ * maxsim or the taken bytes) and L2 and the Infinity Cache can serve its bytes again.
+ *
+ * Accumulation is fp32 and the summation order of a dot product is a function of K and the dtype
+ * alone: the row's 16-byte chunks (8 16-bit or 4 fp32 elements) are dealt to 16 lanes, lane l
+ * taking chunks l, l + 16, ...; a lane starts from +0 and adds product after product with one
+ * fused multiply-add each, its chunks ascending and the elements of a chunk ascending; the 16
+ * lane sums s are then combined as s += s[lane ^ 8], ^ 4, ^ 2, ^ 1. So a row's maxsim has the
+ * same bits wherever the row sits, for any N, on any stream and on every launch, and sel is a
+ * pure function of those values and the lowest-index tie rule.
+ *
+ * Both return AACLIP_ERR_ARG before any launch for NULL pointers, N outside [1, 2^30], m outside
+ * [1, N], start outside [0, N), a dtype outside the three, K % 64 != 0 or K above
+ * AACLIP_CORESET_MAX_K, a stride below K or not 16-byte aligned, misaligned operands or a short
+ * workspace.
+ */
+#define AACLIP_CORESET_MAX_K 4096
+#define AACLIP_CORESET_BLOCK_ROWS 64
+#define AACLIP_CORESET_MAX_BLOCKS 512
+int aaclip_bank_coreset_workspace(int N, size_t* bytes);
+int aaclip_bank_coreset(int dtype, int N, int K, const void* R, int64_t ldr, int m, int start, int32_t* sel,
+                        float* cover, float* maxsim, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Test-time preprocessing (replaces dataset/__init__.py:127-143
  * transform_x / transform_mask, i.e. Pillow's Image.resize as torchvision calls it,
  * then ToTensor + Normalize). Bit-exact with Pillow 8-bit resampling.
