@@ -766,6 +766,39 @@ def _f32rows(t, name, shape=None):
         raise ValueError(f"{name}: row stride must be a multiple of 4 and the start 16-byte aligned")
 
 
+def _overlap(a, b) -> bool:
+    """Whether a and b share a byte. A 2-D tensor with unit column stride is its rows (exact when the
+    two row strides agree or one side is a single row: column views of one buffer do not overlap);
+    anything else must be contiguous and is one range. Two different row strides whose ranges meet
+    count as overlapping."""
+    def rows(t):
+        if t.dim() == 2 and t.stride(1) == 1 and t.shape[0] > 1:
+            return t.data_ptr(), t.shape[0], t.stride(0) * t.element_size(), t.shape[1] * t.element_size()
+        return t.data_ptr(), 1, 0, t.numel() * t.element_size()
+
+    (pa, ra, sa, wa), (pb, rb, sb, wb) = rows(a), rows(b)
+    if min(wa, wb) == 0 or pa + (ra - 1) * sa + wa <= pb or pb + (rb - 1) * sb + wb <= pa:
+        return False
+    s = sa if ra > 1 else sb
+    if s == 0 or (ra > 1 and rb > 1 and sa != sb):
+        return True
+    d = pb - pa  # row i of a meets row j of b iff -wb < d + (j - i) s < wa
+    return max(-(ra - 1), (-wb - d) // s + 1) <= min(rb - 1, -((d - wa) // s) - 1)
+
+
+def _same_view(a, b) -> bool:
+    return a.data_ptr() == b.data_ptr() and a.shape == b.shape and a.stride() == b.stride()
+
+
+def _disjoint(op, out, out_name, *inputs, may_be=()):
+    """out must share no memory with any of the (tensor, name) inputs; the tensors of may_be may
+    instead be out itself, element for element (the kernels read a row before they write it)."""
+    for t, name in inputs:
+        if t is not None and _overlap(out, t) and not (any(t is m for m in may_be) and _same_view(out, t)):
+            raise ValueError(f"{op}: {out_name} overlaps {name}" +
+                             (" without being the same view" if any(t is m for m in may_be) else ""))
+
+
 def _act_mode(mode):
     try:
         return _ACT_MODES[mode]
@@ -809,11 +842,7 @@ def layernorm_bwd(dy, x, w, *, residual=None, out=None):
     if out is None:
         out = torch.empty(rows, width, device=x.device, dtype=torch.float32)
     _f32rows(out, "out", x.shape)
-    if out.data_ptr() == x.data_ptr():
-        raise ValueError("layernorm_bwd: out must not alias x")
-    for t, n in ((dy, "dy"), (residual, "residual")):
-        if t is not None and t.data_ptr() == out.data_ptr() and t.stride(0) != out.stride(0):
-            raise ValueError(f"layernorm_bwd: {n} aliases out with another row stride")
+    _disjoint("layernorm_bwd", out, "out", (x, "x"), (dy, "dy"), (residual, "residual"), may_be=(dy, residual))
     _dev(dy, x, w, residual, out)  # after the shape / dtype checks: those need no device
     _launch("text_bwd", "layernorm_bwd", 0.0, rows * width * 4 * (4 if residual is not None else 3),
             "aaclip_layernorm_bwd", _ptr(dy), dy.stride(0), _ptr(x), x.stride(0), _ptr(w), _ptr(residual),
@@ -837,8 +866,7 @@ def eot_ln_bwd(dy, x, tokens, w, *, out=None):
     if out is None:
         out = torch.empty_like(x)
     _f32c(out, "out", x.shape)
-    if out.data_ptr() in (x.data_ptr(), dy.data_ptr()):
-        raise ValueError("eot_ln_bwd: out must not alias x or dy")
+    _disjoint("eot_ln_bwd", out, "out", (x, "x"), (dy, "dy"))
     for t, nm in ((x, "x"), (dy, "dy"), (w, "w"), (out, "out")):
         if t.data_ptr() % 16:
             raise ValueError(f"eot_ln_bwd: {nm} must be 16-byte aligned")
@@ -887,9 +915,8 @@ def adapter_blend_bwd(dy, x, u, adapt_weight: float, *, dx=None, du=None):
         du = torch.empty_like(x)
     _f32c(dx, "dx", x.shape)
     _f32c(du, "du", x.shape)
-    if dx.data_ptr() in (x.data_ptr(), u.data_ptr()) or \
-            du.data_ptr() in (x.data_ptr(), u.data_ptr(), dy.data_ptr(), dx.data_ptr()):
-        raise ValueError("adapter_blend_bwd: only dx may alias an input (dy)")
+    _disjoint("adapter_blend_bwd", dx, "dx", (x, "x"), (u, "u"), (dy, "dy"), may_be=(dy,))  # dx alone may be dy
+    _disjoint("adapter_blend_bwd", du, "du", (x, "x"), (u, "u"), (dy, "dy"), (dx, "dx"))
     for t in (dy, x, u, dx, du):
         if t.data_ptr() % 16:
             raise ValueError("adapter_blend_bwd operands must be 16-byte aligned")
@@ -911,8 +938,7 @@ def anchor_reduce_bwd(emb, dT, col: int, *, out=None):
     if out is None:
         out = torch.empty_like(emb)
     _f32c(out, "out", emb.shape)
-    if out.data_ptr() == emb.data_ptr():
-        raise ValueError("anchor_reduce_bwd: out must not alias emb")
+    _disjoint("anchor_reduce_bwd", out, "out", (emb, "emb"))
     _dev(emb, dT, out)  # after the shape / dtype checks: those need no device
     _launch("text_bwd", "anchor_reduce_bwd", 0.0, 16.0 * emb.numel(), "aaclip_anchor_reduce_bwd", _ptr(emb), n, dim,
             _ptr(dT), col, dT.shape[1], _ptr(out), _stream())
@@ -945,6 +971,8 @@ def linear_wgrad(dy, x, *, out=None, workspace=None):
         workspace = linear_wgrad_workspace(M, N, K, dy.device)
     if workspace.dtype != torch.float32 or not workspace.is_contiguous():
         raise ValueError("linear_wgrad workspace must be contiguous fp32")
+    _disjoint("linear_wgrad", out, "out", (dy, "dy"), (x, "x"), (workspace, "workspace"))
+    _disjoint("linear_wgrad", workspace, "workspace", (dy, "dy"), (x, "x"))
     _dev(dy, x, out, workspace)  # after the shape / dtype checks: those need no device
     _launch("text_bwd", "linear_wgrad", 2.0 * M * N * K, (M * (N + K) + 2 * N * K) * 4, "aaclip_linear_wgrad",
             _ptr(dy), dy.stride(0), _ptr(x), x.stride(0), M, N, K, _ptr(workspace), workspace.numel() * 4, _ptr(out),
@@ -1019,8 +1047,7 @@ def tap_ln_bwd(dtap, x, w, g, batch: int, n_tok: int):
     _f32c(g, "g", x.shape)
     _f32c(dtap, "dtap", (batch * (n_tok - 1), width))
     _f32c(w, "w", (width,))
-    if g.data_ptr() in (x.data_ptr(), dtap.data_ptr()):
-        raise ValueError("tap_ln_bwd: g must not alias x or dtap")
+    _disjoint("tap_ln_bwd", g, "g", (x, "x"), (dtap, "dtap"))
     for t in (dtap, x, w, g):
         if t.data_ptr() % 16:
             raise ValueError("tap_ln_bwd operands must be 16-byte aligned")
@@ -1044,10 +1071,8 @@ def l2_normalize_bwd(dy, x, *, group: int = 0, scale: float = 1.0, out=None):
     if out is None:
         out = torch.empty(rows, width, device=x.device, dtype=torch.float32)
     _f32rows(out, "out", x.shape)
-    if out.data_ptr() == x.data_ptr():
-        raise ValueError("l2_normalize_bwd: out must not alias x")
-    if out.data_ptr() == dy.data_ptr() and (group or out.stride(0) != dy.stride(0)):
-        raise ValueError("l2_normalize_bwd: out may alias dy only row for row")
+    # out may be dy only row for row: never under a group
+    _disjoint("l2_normalize_bwd", out, "out", (x, "x"), (dy, "dy"), may_be=() if group else (dy,))
     _dev(dy, x, out)  # after the shape / dtype checks: those need no device
     _launch("visual_bwd", "l2_normalize_bwd", 0.0, 12.0 * rows * width, "aaclip_l2_normalize_bwd", _ptr(dy),
             dy.stride(0), int(group), float(scale), _ptr(x), x.stride(0), _ptr(out), out.stride(0), rows, width,
