@@ -102,6 +102,10 @@ SIGNATURES = {
     "aaclip_overlay_workspace": [_I, ctypes.POINTER(ctypes.c_size_t)],
     "aaclip_overlay_range": [_P, _I, _L, _P, ctypes.c_size_t, _P, _P],
     "aaclip_overlay_panels": [_P, _P, _P, _P, _I, _I, _I, _P, _P],
+    "aaclip_tile_plan": [_I, _I, _I, _P, _P],
+    "aaclip_tile_gather": [_P, _I, _I, _I, _I, _L, _L, _P, _P],
+    "aaclip_tile_stitch": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P],
+    "aaclip_tile_score": [_P, _P, _I, _I, _F, _P, _P],
     "aaclip_bicubic_taps": [_I, _I, ctypes.POINTER(_I)],
     "aaclip_bicubic_plan": [_I, _I, _P, _P, _I],
     "aaclip_nearest_plan": [_I, _I, _P],

@@ -1010,6 +1010,72 @@ class VisualEngine:
         self._graph_cache[key] = run  # most recently used last
         return run(x, T.to(self.device, torch.float32))
 
+    # ------------------------------------------------------------------ tiled inference
+    @torch.no_grad()
+    @_on_device
+    def predict_tiled(self, canvas: torch.Tensor, T: torch.Tensor, grid: int, overlap: int,
+                      domain: str = "Industrial", global_view: torch.Tensor | None = None,
+                      global_weight: float = 0.5, streams=1, tile_batch: int = 32):
+        """Sliding-window inference at the native scale (no reference counterpart): canvas fp32
+        [B, 3, C, C] is cut into grid x grid tiles of side S = (C + (grid - 1) overlap) / grid
+        overlapping by `overlap` pixels (include/aaclip.h, tiled inference), every tile goes through
+        predict at S, and the tile maps are stitched onto the canvas. Returns (map [B, C, C], score
+        [B]) fp32, fresh tensors:
+          map   = (1 - a) * blend-weighted sum of the covering tile maps + a * the global view's map
+                  upsampled bilinearly to C x C
+          score = (1 - a) * max over the image's tiles + a * the global view's score
+        with a = global_weight in [0, 1) and global_view [B, 3, S, S] the whole photo at the tile
+        size; a = 0 runs no global forward and reads no global_view. The tiles are gathered and run
+        tile_batch at a time through predict_cached (so a repeated tile-batch shape replays its
+        captured graph in the same workspaces; the last chunk may be ragged), each chunk's
+        engine-owned outputs copied into a per-(B, S, grid) buffer before the next call; the global
+        view goes through the same path. An image's result does not depend on B, tile_batch or
+        streams. ValueError when S is no integer or not the size of the tower's positional
+        embedding, or when a > 0 and global_view is missing or of another shape."""
+        if canvas.dim() != 4 or canvas.shape[1] != 3 or canvas.shape[2] != canvas.shape[3] or canvas.shape[0] < 1:
+            raise ValueError(f"canvas must be a non-empty [B, 3, C, C], got {tuple(canvas.shape)}")
+        B, C, G, O = canvas.shape[0], canvas.shape[-1], int(grid), int(overlap)
+        S = ops.tile_side(C, G, O)
+        if S % PATCH:
+            raise ValueError(f"a canvas of {C} px in {G} x {G} tiles overlapping by {O} gives tiles of {S} px, "
+                             f"no multiple of {PATCH}")
+        _check_pos(self.pos, (S // PATCH) ** 2 + 1)
+        a = float(global_weight)
+        if not 0.0 <= a < 1.0:
+            raise ValueError(f"global_weight must lie in [0, 1), got {global_weight}")
+        if a > 0.0 and (global_view is None or tuple(global_view.shape) != (B, 3, S, S)):
+            raise ValueError(f"global_weight {a} needs global_view {(B, 3, S, S)}, got "
+                             f"{None if global_view is None else tuple(global_view.shape)}")
+        tile_batch = int(tile_batch)
+        if tile_batch < 1:
+            raise ValueError(f"tile_batch must be at least 1, got {tile_batch}")
+        canvas = canvas.to(self.device, torch.float32).contiguous()
+        n = B * G * G
+        step = min(tile_batch, n, self.max_chunk(S))
+        if not hasattr(self, "_tiled"):
+            self._tiled = {}
+        key = (B, S, G)
+        if key not in self._tiled:
+            for k in [k for k in self._tiled if k[1] != S]:  # as _workspace: one image size resident
+                del self._tiled[k]
+            self._tiled[key] = (torch.empty(n, S, S, device=self.device), torch.empty(n, device=self.device))
+        tile_maps, tile_scores = self._tiled[key]
+        stage = self._tiled.get(("stage", S, step))
+        if stage is None:
+            stage = self._tiled[("stage", S, step)] = torch.empty(step, 3, S, S, device=self.device)
+        for t0 in range(0, n, step):
+            t1 = min(n, t0 + step)
+            tiles = ops.tile_gather(canvas, G, O, tiles=(t0, t1), out=stage[:t1 - t0])
+            m, s = self.predict_cached(tiles, T, domain, streams=streams)
+            tile_maps[t0:t1].copy_(m)
+            tile_scores[t0:t1].copy_(s)
+        gmap = gscore = None
+        if a > 0.0:  # last: its engine-owned outputs are read by the stitch before any other predict
+            gmap, gscore = self.predict_cached(global_view, T, domain, streams=streams)
+        out_map = ops.tile_stitch(tile_maps, G, O, global_maps=gmap, global_weight=a)
+        out_score = ops.tile_score(tile_scores, G, global_scores=gscore, global_weight=a)
+        return out_map, out_score
+
     @torch.no_grad()
     @_on_device
     def graphed_predict(self, batch: int, img_size: int, domain: str = "Industrial", streams: int = 1):

@@ -1801,3 +1801,152 @@ def fewshot_fuse(zs_map, fs_map, zs_score):
         call("aaclip_fewshot_fuse", _ptr(zs_map), _ptr(fs_map), _ptr(zs_score), n, zs_map.numel() // n, at, nbytes,
              _ptr(fused_map), _ptr(fs_score), _ptr(fused_score), _stream())
     return fused_map, fs_score, fused_score
+
+
+# ------------------------------------------------------------------------ tiled inference
+TILE_MAX_GRID = 8  # tiles per axis (csrc/tiles.hip)
+
+
+def tile_canvas(S: int, G: int, O: int) -> int:
+    """Canvas side of G x G tiles of side S overlapping by O pixels: G S - (G - 1) O. Raises
+    ValueError outside 2 <= G <= 8, 0 <= O <= S // 2."""
+    S, G, O = int(S), int(G), int(O)
+    if S < 1 or not 2 <= G <= TILE_MAX_GRID or not 0 <= 2 * O <= S:
+        raise ValueError(f"tiling needs a tile side >= 1, 2 <= grid <= {TILE_MAX_GRID} and 0 <= overlap <= side // 2, "
+                         f"got side {S}, grid {G}, overlap {O}")
+    return G * S - (G - 1) * O
+
+
+def tile_side(C: int, G: int, O: int) -> int:
+    """Tile side of a canvas of side C cut into G x G tiles overlapping by O: (C + (G - 1) O) / G,
+    ValueError when that is no integer or the geometry is out of range."""
+    C, G, O = int(C), int(G), int(O)
+    if not 2 <= G <= TILE_MAX_GRID or O < 0 or C < 1 or (C + (G - 1) * O) % G:
+        raise ValueError(f"a canvas of side {C} is not {G} x {G} tiles overlapping by {O} pixels")
+    S = (C + (G - 1) * O) // G
+    tile_canvas(S, G, O)
+    return S
+
+
+def tile_plan(S: int, G: int, O: int):
+    """The per-axis tables of aaclip_tile_plan (host only): (index int32 [C, 2] = first covering
+    tile, bilinear source cell i0; weight float32 [C, 4] = the first tile's weight, the next tile's
+    or 0, 1 - lambda, lambda), C = tile_canvas(S, G, O). One pair serves rows and columns."""
+    import numpy as np
+    C = tile_canvas(S, G, O)
+    index, weight = np.zeros((C, 2), np.int32), np.zeros((C, 4), np.float32)
+    call("aaclip_tile_plan", int(S), int(G), int(O), index.ctypes.data_as(ctypes.c_void_p),
+         weight.ctypes.data_as(ctypes.c_void_p))
+    return index, weight
+
+
+_tile_plans: dict = {}
+
+
+def _tile_tables(S, G, O, device):
+    key = (int(S), int(G), int(O), device)
+    if key not in _tile_plans:
+        index, weight = tile_plan(S, G, O)
+        _tile_plans[key] = (torch.from_numpy(index).to(device), torch.from_numpy(weight).to(device))
+    return _tile_plans[key]
+
+
+def _tile_weight(global_weight, operand, name):
+    a = float(global_weight)
+    if not 0.0 <= a < 1.0:
+        raise ValueError(f"{name}: global_weight must lie in [0, 1), got {global_weight}")
+    if a > 0.0 and operand is None:
+        raise ValueError(f"{name}: a global weight above 0 needs the global view's result")
+    return a
+
+
+def tile_gather(canvas, grid: int, overlap: int, *, images=None, tiles=None, out=None):
+    """The tiles of a canvas as one batch (aaclip_tile_gather, a pure copy): canvas fp32 contiguous
+    [n, 3, C, C] -> fp32 [k, 3, S, S], row b G^2 + ty G + tx = canvas[b, :, oy:oy+S, ox:ox+S] with
+    the origin (ty, tx) (S - O). images = (b0, b1) gathers those images' tiles, tiles = (t0, t1)
+    that run of tile rows (a chunk need not end on an image); neither = all of them."""
+    if canvas.dim() != 4 or canvas.shape[1] != 3 or canvas.shape[2] != canvas.shape[3] or canvas.numel() == 0:
+        raise ValueError(f"tile_gather: canvas must be a non-empty [n, 3, C, C], got {tuple(canvas.shape)}")
+    if canvas.dtype != torch.float32 or not canvas.is_contiguous():
+        raise ValueError("tile_gather: canvas must be contiguous float32")
+    n, G, O = canvas.shape[0], int(grid), int(overlap)
+    S = tile_side(canvas.shape[-1], G, O)
+    if images is not None and tiles is not None:
+        raise ValueError("tile_gather: give images or tiles, not both")
+    t0, t1 = (0, n * G * G) if tiles is None else (int(tiles[0]), int(tiles[1]))
+    if images is not None:
+        t0, t1 = int(images[0]) * G * G, int(images[1]) * G * G
+    if not 0 <= t0 < t1 <= n * G * G:
+        raise ValueError(f"tile_gather: tile rows [{t0}, {t1}) lie outside the canvas batch's {n * G * G}")
+    if out is None:
+        out = torch.empty(t1 - t0, 3, S, S, device=canvas.device, dtype=torch.float32)
+    if tuple(out.shape) != (t1 - t0, 3, S, S) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"tile_gather: out must be a contiguous float32 {(t1 - t0, 3, S, S)}")
+    with torch.cuda.device(canvas.device):
+        _dev(canvas, out)
+        _launch("tiles", "tile_gather", 0.0, 8.0 * out.numel(), "aaclip_tile_gather", _ptr(canvas), n, S, G, O, t0,
+                t1 - t0, _ptr(out), _stream())
+    return out
+
+
+def tile_stitch(tile_maps, grid: int, overlap: int, *, global_maps=None, global_weight: float = 0.0, out=None):
+    """The tile maps put back together on the canvas (aaclip_tile_stitch): tile_maps fp32 contiguous
+    [B G^2, S, S], image-major -> fp32 [B, C, C], every pixel the blend-weighted sum of the one, two
+    or four tile pixels covering it; with global_weight a in (0, 1), (1 - a) times that plus a times
+    global_maps [B, S, S] upsampled bilinearly (half-pixel centres). With a = 0 global_maps is not
+    read. One writer per pixel in a fixed term order: deterministic. The tables are built on the
+    host once per (S, G, O, device)."""
+    G, O = int(grid), int(overlap)
+    if tile_maps.dim() != 3 or tile_maps.shape[1] != tile_maps.shape[2] or tile_maps.numel() == 0 or \
+            tile_maps.shape[0] % (G * G if 2 <= G <= TILE_MAX_GRID else 1):
+        raise ValueError(f"tile_stitch: tile_maps must be a non-empty [B * {G * G}, S, S], got {tuple(tile_maps.shape)}")
+    if tile_maps.dtype != torch.float32 or not tile_maps.is_contiguous():
+        raise ValueError("tile_stitch: tile_maps must be contiguous float32")
+    S = tile_maps.shape[-1]
+    C = tile_canvas(S, G, O)
+    B = tile_maps.shape[0] // (G * G)
+    a = _tile_weight(global_weight, global_maps, "tile_stitch")
+    if a == 0.0:
+        global_maps = None
+    elif tuple(global_maps.shape) != (B, S, S) or global_maps.dtype != torch.float32 or not global_maps.is_contiguous():
+        raise ValueError(f"tile_stitch: global_maps must be a contiguous float32 {(B, S, S)}")
+    if out is None:
+        out = torch.empty(B, C, C, device=tile_maps.device, dtype=torch.float32)
+    if tuple(out.shape) != (B, C, C) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"tile_stitch: out must be a contiguous float32 {(B, C, C)}")
+    with torch.cuda.device(tile_maps.device):
+        _dev(tile_maps, global_maps, out)
+        index, weight = _tile_tables(S, G, O, tile_maps.device)
+        nbytes = 4.0 * (out.numel() + tile_maps.numel() + (0 if global_maps is None else global_maps.numel()))
+        _launch("tiles", "tile_stitch", 0.0, nbytes, "aaclip_tile_stitch", _ptr(tile_maps), _ptr(global_maps),
+                _ptr(index), _ptr(weight), B, S, G, O, a, _ptr(out), _stream())
+    return out
+
+
+def tile_score(tile_scores, grid: int, *, global_scores=None, global_weight: float = 0.0, out=None):
+    """Image scores of a tiled batch (aaclip_tile_score): tile_scores fp32 [B G^2] image-major ->
+    fp32 [B] = (1 - a) max over the image's tiles + a global_scores[b]; with a = 0 the maximum
+    itself. Enqueued without a host sync."""
+    G = int(grid)
+    if not 2 <= G <= TILE_MAX_GRID:
+        raise ValueError(f"tile_score: 2 <= grid <= {TILE_MAX_GRID}, got {grid}")
+    if tile_scores.dim() != 1 or tile_scores.numel() == 0 or tile_scores.numel() % (G * G):
+        raise ValueError(f"tile_score: tile_scores must be a non-empty [B * {G * G}], got {tuple(tile_scores.shape)}")
+    if tile_scores.dtype != torch.float32 or not tile_scores.is_contiguous():
+        raise ValueError("tile_score: tile_scores must be contiguous float32")
+    B = tile_scores.numel() // (G * G)
+    a = _tile_weight(global_weight, global_scores, "tile_score")
+    if a == 0.0:
+        global_scores = None
+    elif tuple(global_scores.shape) != (B,) or global_scores.dtype != torch.float32 or \
+            not global_scores.is_contiguous():
+        raise ValueError(f"tile_score: global_scores must be a contiguous float32 {(B,)}")
+    if out is None:
+        out = torch.empty(B, device=tile_scores.device, dtype=torch.float32)
+    if tuple(out.shape) != (B,) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"tile_score: out must be a contiguous float32 {(B,)}")
+    with torch.cuda.device(tile_scores.device):
+        _dev(tile_scores, global_scores, out)
+        _launch("tiles", "tile_score", 0.0, 4.0 * (tile_scores.numel() + 2 * B), "aaclip_tile_score",
+                _ptr(tile_scores), _ptr(global_scores), B, G, a, _ptr(out), _stream())
+    return out

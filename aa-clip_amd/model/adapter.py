@@ -157,6 +157,20 @@ class AdaptedCLIP(nn.Module):
         The outputs are engine-owned buffers: clone them to keep them (test.py does)."""
         return self.visual_engine().predict_cached(x, text_features, domain, streams=streams)
 
+    def predict_tiled(self, canvas, text_features, grid, overlap, domain="Industrial", global_view=None,
+                      global_weight=0.5, streams=1, tile_batch=32):
+        """Sliding-window test path at the native scale (no reference counterpart): canvas
+        [B, 3, C, C] is cut into grid x grid tiles of the tower's image size S overlapping by
+        `overlap` pixels (C = grid S - (grid - 1) overlap), each tile runs through predict, and the
+        tile maps are stitched on the device with linear ramps across the overlaps. Returns
+        (anomaly map [B, C, C], image score [B]), fp32, fresh tensors: the map mixed with the
+        bilinearly upsampled map of global_view [B, 3, S, S] (the whole photo at S) by
+        global_weight in [0, 1), the score the tiles' maximum mixed with the global view's score
+        the same way; global_weight 0 runs no global forward. tile_batch tiles run per predict
+        call; results do not depend on it, on B or on streams (VisualEngine.predict_tiled)."""
+        return self.visual_engine().predict_tiled(canvas, text_features, grid, overlap, domain, global_view,
+                                                  global_weight, streams, tile_batch)
+
     def build_memory_bank(self, images, search_dtype=None, coreset=None):
         """The few-shot memory bank of a class from its normal support images [k, 3, S, S]
         (reference test.py:39-50, get_support_features): VisualEngine.build_bank. search_dtype

@@ -32,7 +32,12 @@ Differences from the reference, all on the host side:
     values) and searches on the block-scaled fp8 MFMA, the cosine taken between the stored rows;
     the default searches in the engine's own search dtype. --bank_coreset RATIO keeps per level
     only that share of the bank's rows, a greedy k-centre coreset selected on the device (the
-    subsampling of the PatchCore family of memory-bank detectors; the reference has none).
+    subsampling of the PatchCore family of memory-bank detectors; the reference has none);
+  * --tile_grid G (G >= 2; the reference has one input shape) runs sliding-window inference at the
+    native scale: every photo is brought to a canvas of C = G S - (G - 1) O pixels (S = --img_size,
+    O = --tile_overlap), cut into G x G tiles of S pixels, each tile goes through the tower, and the
+    tile maps are stitched on the device and mixed with the map of the whole photo at S
+    (--tile_global_weight). Masks, maps, metrics, regions and overlays are then C x C.
 """
 from __future__ import annotations
 
@@ -54,13 +59,16 @@ from model.clip import create_model  # noqa: E402
 from utils import setup_seed  # noqa: E402
 
 
-def _device_batch(input_data, prep, device, thumbs=None):
+def _device_batch(input_data, prep, device, thumbs=None, *, views=None, global_prep=None, global_size=None):
     """One loader batch -> (image fp32 [B,3,S,S], mask uint8 [B,1,S,S]) on the device:
     raw uint8 batches (dataset raw=True) go through aaclip_preprocess_images /
     aaclip_resize_masks_nearest, normalised ones are copied (non_blocking from the
     DataLoader's pinned memory). Runs on the caller's current stream. thumbs (a list, raw
     batches only): the batch's uint8 [B,S,S,3] thumbnails for visualize() are appended to it,
-    resized from the same device copy of the photos (aaclip_resize_bilinear_u8)."""
+    resized from the same device copy of the photos (aaclip_resize_bilinear_u8). views (a list,
+    --tile_grid): the batch's global view fp32 [B,3,global_size,global_size] is appended to it, for
+    raw batches made by global_prep from the same device copy of the photos (prep then makes the
+    canvas), for normalised ones pooled from the canvas."""
     if prep is not None:
         def to_dev(u8):
             if isinstance(u8, torch.Tensor):
@@ -74,14 +82,20 @@ def _device_batch(input_data, prep, device, thumbs=None):
         if thumbs is not None:
             from aaclip import ops
             thumbs.append(run(lambda t: ops.resize_bilinear_u8(t, prep.S), image_u8))
+        if views is not None:
+            views.append(run(global_prep.images, image_u8))
     else:
         image = input_data["image"].to(device, non_blocking=True)
         mask = torch.as_tensor(input_data["mask"]).to(device, non_blocking=True)
+        if views is not None:
+            # harness code, not a model of any camera: the synthetic items exist only at the canvas
+            # size, so their "whole photo at S" is the canvas area-averaged down to S
+            views.append(torch.nn.functional.adaptive_avg_pool2d(image, int(global_size)))
     return image, (mask != 0).to(torch.uint8)
 
 
 def get_predictions(model, class_text_embeddings, test_loader, device, img_size, dataset="MVTec", prep=None,
-                    n_total=None, streams=1, sources=None):
+                    n_total=None, streams=1, sources=None, tiling=None, global_prep=None, tile_batch=32):
     """test.py:53-99. Batch k+1 is copied to the device (and preprocessed, with prep) on a
     copy stream while batch k runs; maps, scores and masks stay on the device (the
     reference syncs twice per batch, test.py:85,93). Returns (masks uint8 [N,1,S,S]
@@ -93,7 +107,11 @@ def get_predictions(model, class_text_embeddings, test_loader, device, img_size,
     streams) for batches of at least 8 images per chunk; results do not depend on it.
     sources (a list; single-process raw mode, i.e. with prep and without n_total): each batch's
     uint8 [B,S,S,3] thumbnails are appended to it, made at batch time from the photos already
-    on the device, so visualize() decodes nothing twice. Otherwise it is left empty."""
+    on the device, so visualize() decodes nothing twice. Otherwise it is left empty.
+    tiling ({"grid", "overlap", "canvas", "global_weight"}, --tile_grid): every batch arrives at
+    the canvas size (prep, or the dataset, makes it) and goes through model.predict_tiled, tile_batch
+    tiles per tower call, with the global view at img_size (global_prep for raw batches); masks and
+    maps, the empty shard's zero rows included, are then canvas x canvas."""
     masks, labels, preds, preds_image, file_names = [], [], [], [], []
     device = torch.device(device)
     on_gpu = device.type == "cuda"  # (a CPU device only in the host-logic tests, with a stand-in model)
@@ -101,26 +119,32 @@ def get_predictions(model, class_text_embeddings, test_loader, device, img_size,
     copy = torch.cuda.Stream(device=device) if on_gpu else None
 
     want_thumbs = sources is not None and prep is not None and n_total is None
+    want_view = tiling is not None and tiling["global_weight"] > 0
+    out_size = tiling["canvas"] if tiling is not None else img_size
 
     def stage(batch):
         thumbs = [] if want_thumbs else None
+        views = [] if want_view else None
+        extra = dict(views=views, global_prep=global_prep, global_size=img_size) if want_view else {}
         if not on_gpu:
-            return (batch,) + _device_batch(batch, prep, device, thumbs) + (None, thumbs)
+            return (batch,) + _device_batch(batch, prep, device, thumbs, **extra) + (None, thumbs, views)
         with torch.cuda.stream(copy):
-            image, mask = _device_batch(batch, prep, device, thumbs)
+            image, mask = _device_batch(batch, prep, device, thumbs, **extra)
         ev = torch.cuda.Event()
         ev.record(copy)
-        return batch, image, mask, ev, thumbs
+        return batch, image, mask, ev, thumbs, views
 
     it = iter(test_loader)
     first = next(it, None)
     staged = stage(first) if first is not None else None
     while staged is not None:
-        input_data, image, mask, ready, thumbs = staged
+        input_data, image, mask, ready, thumbs, views = staged
         if on_gpu:
             main.wait_event(ready)
             image.record_stream(main)
             mask.record_stream(main)
+            if views:
+                views[0].record_stream(main)
         if thumbs:
             if on_gpu:
                 thumbs[0].record_stream(main)
@@ -129,10 +153,19 @@ def get_predictions(model, class_text_embeddings, test_loader, device, img_size,
         assert len(set(class_name)) == 1, "mixed class not supported"
         labels.append(np.asarray(input_data["label"]))
         file_names.extend(input_data["file_name"])
-        nst = streams if image.shape[0] >= 8 * streams else 1
-        pmap, score = model.predict(image, class_text_embeddings, DOMAINS[dataset], streams=nst)
-        preds.append(pmap.clone())
-        preds_image.append(score.clone())
+        if tiling is not None:  # fresh tensors
+            n_tiles = min(int(tile_batch), image.shape[0] * tiling["grid"] ** 2)
+            pmap, score = model.predict_tiled(image, class_text_embeddings, tiling["grid"], tiling["overlap"],
+                                              DOMAINS[dataset], global_view=views[0] if views else None,
+                                              global_weight=tiling["global_weight"],
+                                              streams=streams if n_tiles >= 8 * streams else 1, tile_batch=tile_batch)
+            preds.append(pmap)
+            preds_image.append(score)
+        else:
+            nst = streams if image.shape[0] >= 8 * streams else 1
+            pmap, score = model.predict(image, class_text_embeddings, DOMAINS[dataset], streams=nst)
+            preds.append(pmap.clone())
+            preds_image.append(score.clone())
         masks.append(mask)
         nxt = next(it, None)  # host: the next batch (loader workers) while this one runs
         staged = stage(nxt) if nxt is not None else None
@@ -140,9 +173,9 @@ def get_predictions(model, class_text_embeddings, test_loader, device, img_size,
         masks, labels = torch.cat(masks), np.concatenate(labels, axis=0)
         preds, preds_image = torch.cat(preds), torch.cat(preds_image)
     else:  # empty shard (fewer images than ranks): zero rows of the right shapes
-        masks = torch.zeros(0, 1, img_size, img_size, device=device, dtype=torch.uint8)
+        masks = torch.zeros(0, 1, out_size, out_size, device=device, dtype=torch.uint8)
         labels = np.zeros(0, dtype=np.int64)
-        preds = torch.zeros(0, img_size, img_size, device=device)
+        preds = torch.zeros(0, out_size, out_size, device=device)
         preds_image = torch.zeros(0, device=device)
     if n_total is not None:
         import torch.distributed as dist
@@ -274,9 +307,30 @@ def parse_args(argv=None):
     parser.add_argument("--regions_min_area", type=int, default=1, help="--regions: drop smaller regions")
     parser.add_argument("--regions_max", type=int, default=64,
                         help="--regions: regions listed per image, the largest first (all are counted)")
+    parser.add_argument("--tile_grid", type=int, default=1, metavar="G",
+                        help="sliding-window inference at the native scale: G x G tiles of --img_size pixels per "
+                             "photo, stitched on the device (2..8; 1 = off, the whole photo at --img_size)")
+    parser.add_argument("--tile_overlap", type=int, default=None, metavar="O",
+                        help="--tile_grid: pixels neighbouring tiles share, blended with linear ramps; 0 .. "
+                             "img_size // 2 (default img_size // 4). The canvas is G * img_size - (G - 1) * O pixels")
+    parser.add_argument("--tile_global_weight", type=float, default=0.5, metavar="A",
+                        help="--tile_grid: weight in [0, 1) of the whole photo's map and score at --img_size in "
+                             "the result (0 = tiles only, no global forward)")
     args = parser.parse_args(argv)
     if args.regions:
         args.f1 = True
+    if args.tile_overlap is None:
+        args.tile_overlap = args.img_size // 4
+    if args.tile_grid != 1:
+        if not 2 <= args.tile_grid <= 8:
+            parser.error(f"--tile_grid takes 1 (off) or 2..8, got {args.tile_grid}")
+        if args.few_shot:
+            parser.error("--tile_grid with --few_shot is not supported: the memory bank would need tile-scale rows")
+        if not 0 <= args.tile_overlap <= args.img_size // 2:
+            parser.error(f"--tile_overlap must lie in 0 .. img_size // 2 = {args.img_size // 2}, got "
+                         f"{args.tile_overlap}")
+        if not 0.0 <= args.tile_global_weight < 1.0:
+            parser.error(f"--tile_global_weight must lie in [0, 1), got {args.tile_global_weight}")
     return args
 
 
@@ -292,7 +346,8 @@ def run(args):
     "n_regions", "regions"}]}, see forward_utils.anomaly_regions, with --few_shot also
     "few_shot": per class the device tensors zs_map, fs_map, fused_map, zs_score, fs_score,
     fused_score and "bank", the kept / source rows and the coreset's coverage per level; the
-    class's preds and preds_image are then the fused ones) for callers/tests."""
+    class's preds and preds_image are then the fused ones, with --tile_grid also "tiling": {"grid",
+    "overlap", "canvas", "global_weight"}, masks and preds then canvas x canvas) for callers/tests."""
     setup_seed(args.seed)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -360,16 +415,27 @@ def run(args):
         logger.info("-----------------------------------------------")
         synthetic = args.dataset.startswith("synthetic")
         raw = args.gpu_preprocess and not synthetic  # synthetic items are already normalised
-        image_datasets = get_dataset(args.dataset, args.img_size, None, args.shot, "test", logger=logger,
+        tiling, data_size = None, args.img_size
+        if args.tile_grid > 1:  # photos, masks and thumbnails at the canvas size; the model stays at img_size
+            if not raw and not synthetic:
+                raise RuntimeError("--tile_grid on a real dataset needs --gpu_preprocess: the canvas and the "
+                                   "global view are made from one device copy of the photo")
+            data_size = args.tile_grid * args.img_size - (args.tile_grid - 1) * args.tile_overlap
+            tiling = {"grid": args.tile_grid, "overlap": args.tile_overlap, "canvas": data_size,
+                      "global_weight": args.tile_global_weight}
+            logger.info("tiling: %s", tiling)
+        image_datasets = get_dataset(args.dataset, data_size, None, args.shot, "test", logger=logger,
                                      synthetic_n=args.synthetic_n, raw=raw)
         support_datasets = None
         if args.few_shot:  # before any model work: a real dataset without --support_meta fails here
             support_datasets = get_dataset(args.dataset, args.img_size, None, args.shot, "support", raw=raw,
                                            support_meta=args.support_meta or None)
-        prep = None
+        prep = global_prep = None
         if raw:
             from aaclip.preprocess import Preprocessor
-            prep = Preprocessor(args.img_size)
+            prep = Preprocessor(data_size)
+            if tiling is not None:
+                global_prep = Preprocessor(args.img_size)
         with torch.no_grad():
             text_embeddings = get_adapted_text_embedding(model if adapt_text else clip_model, args.dataset, device)
         df = DataFrame(columns=["class name", "pixel AUC", "pixel AP", "image AUC", "image AP"]
@@ -377,6 +443,8 @@ def run(args):
                        + (["pixel F1-max", "image F1-max"] if args.f1 else []))
         pending = []
         ctx = {"model": model, "text_embeddings": text_embeddings, "classes": {}}
+        if tiling is not None:
+            ctx["tiling"] = tiling
         if args.f1:
             ctx["operating_points"] = {}
         if args.regions:
@@ -415,7 +483,8 @@ def run(args):
                     masks, labels, preds, preds_image, file_names = get_predictions(
                         model=model, class_text_embeddings=text_embeddings[class_name], test_loader=loader,
                         device=device, img_size=args.img_size, dataset=args.dataset, prep=prep, n_total=n_total,
-                        streams=args.streams, sources=sources)
+                        streams=args.streams, sources=sources,
+                        **(dict(tiling=tiling, global_prep=global_prep, tile_batch=args.batch_size) if tiling else {}))
             if rank != 0:  # the class was gathered onto rank 0, which runs metrics_eval
                 continue
             if args.visualize:
@@ -471,6 +540,8 @@ def run(args):
                     table["operating_points"] = ctx["operating_points"]
                 if args.regions:
                     table["regions"] = ctx["regions"]
+                if tiling is not None:
+                    table["tiling"] = tiling
                 json.dump(table, f)
     return df, ctx
 

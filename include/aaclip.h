@@ -873,6 +873,63 @@ int aaclip_overlay_panels(const float* maps, const uint8_t* labels, const uint8_
                           int batch, int size, int swap_rb, uint8_t* out, void* stream);
 
 /*
+ * Tiled high-resolution inference (csrc/tiles.hip); no reference counterpart: the reference has
+ * one input shape, the whole photo resized to img_size squared. A C x C canvas is cut into G x G
+ * overlapping S x S tiles, every tile goes through the tower at the native scale, the tile maps
+ * are stitched back onto the canvas and may be mixed with the map of a global view (the whole
+ * photo at S x S). tests/tiled_ref.py states all of it in numpy float64.
+ *
+ * Geometry: tile side S, G tiles per axis (2 <= G <= 8), overlap O pixels (0 <= O <= S / 2),
+ * canvas side C = G S - (G - 1) O. Tile (ty, tx) has origin (ty (S - O), tx (S - O)) and index
+ * t = ty G + tx; the tiles of image b are rows b G^2 + t, image-major. With O <= S / 2 at most two
+ * tiles cover a canvas coordinate per axis. The 1-D blend weight of tile i at local coordinate u is
+ * (u + 0.5) / O for u < O when i > 0, (S - u - 0.5) / O for u >= S - O when i < G - 1 and 1
+ * elsewhere (the canvas borders get 1); in an overlap the two ramps sum to 1 in real arithmetic, so
+ * nothing is divided by a weight sum. A pixel's weight is the product of its two 1-D weights.
+ * The global view's map is upsampled to C x C bilinearly with half-pixel centres and a clamp at 0
+ * (F.interpolate(mode="bilinear", align_corners=False)): per axis i0 = floor(((2 x + 1) S - C) /
+ * (2 C)), clamped at 0, lambda = the remainder over 2 C (0 where clamped), i1 = min(i0 + 1, S - 1).
+ *
+ * aaclip_tile_plan (host only, no device work): the per-axis tables of one (S, G, O); the canvas and
+ * the grid are square, so the same tables serve rows and columns. index int32 [C, 2] = (first
+ * covering tile, i0); weight fp32 [C, 4] = (that tile's weight, the next tile's or 0 where one tile
+ * covers, 1 - lambda, lambda). Everything comes from integer arithmetic, each weight computed in
+ * double and rounded once to fp32.
+ *
+ * aaclip_tile_gather: tiles[k] = canvas[b, :, oy : oy + S, ox : ox + S] for the tile rows
+ * tile0 + k = b G^2 + t, k in [0, n_tiles): a pure copy of fp32 values. canvas fp32
+ * [n_images, 3, C, C], tiles fp32 [n_tiles, 3, S, S], both contiguous; any run of tile rows inside
+ * [0, n_images G^2), so a caller can gather a chunk of images, or of tiles, at a time. Needs
+ * 3 n_images G^2 < 2^31.
+ *
+ * aaclip_tile_stitch: with a = global_weight in [0, 1), both coefficients fp32 (1 - a rounded once),
+ *   out[b, y, x] = (1 - a) * sum over the covering tiles, ty then tx, of
+ *                      (wy * wx) * tile_maps[b G^2 + t, y - oy, x - ox]
+ *                  + a * (((ly0 * lx0) * g[iy0, ix0] + (ly0 * lx1) * g[iy0, ix1])
+ *                         + (ly1 * lx0) * g[iy1, ix0]) + (ly1 * lx1) * g[iy1, ix1]),  g = global_maps[b]
+ * every product and sum one rounded fp32 operation in that order (no FMA contraction); a tile that
+ * does not cover the pixel contributes no term. With a == 0 the result is the tile sum itself and
+ * global_maps is not read (it may be NULL). tile_maps fp32 [batch G^2, S, S], global_maps fp32
+ * [batch, S, S], index / weight device copies of the plan's tables (weight 16-byte aligned), out
+ * fp32 [batch, C, C]. One writer per output pixel, no atomics: the same bits on every launch.
+ * Offsets are 64-bit; needs batch C < 2^31. Table indices are clamped to what exists.
+ *
+ * aaclip_tile_score: out[b] = (1 - a) * max over t of tile_scores[b G^2 + t] + a * global_scores[b],
+ * fp32; with a == 0 the maximum itself, global_scores not read (may be NULL).
+ *
+ * All of them return AACLIP_ERR_ARG, before any launch, for NULL pointers, non-positive sizes, G
+ * outside [2, 8], O outside [0, S / 2], a tile range outside the canvas batch, a global weight
+ * outside [0, 1) or misaligned operands; the device entries allocate nothing and do not sync.
+ */
+int aaclip_tile_plan(int S, int G, int O, int32_t* index, float* weight);
+int aaclip_tile_gather(const float* canvas, int n_images, int S, int G, int O, int64_t tile0, int64_t n_tiles,
+                       float* tiles, void* stream);
+int aaclip_tile_stitch(const float* tile_maps, const float* global_maps, const int32_t* index, const float* weight,
+                       int batch, int S, int G, int O, float global_weight, float* out, void* stream);
+int aaclip_tile_score(const float* tile_scores, const float* global_scores, int batch, int G, float global_weight,
+                      float* out, void* stream);
+
+/*
  * Few-shot memory-bank scoring (csrc/bank.hip). Replaces what the reference carries for it and
  * wires to nothing: test.py:39-50 get_support_features (the bank: the level features of a few
  * normal support images, concatenated per level) and utils.py:86-93 cos_sim (the patch x bank
